@@ -4,7 +4,7 @@ One step = the reference hot loop (train.py:89-96) on a synthetic batch already 
 softmax cross-entropy, zero_grad(set_to_none), backward (+ RCCL gradient all-reduce overlapped with it when N > 1),
 FusedAdamW step.  Weak scaling: every rank processes its own batch of 256.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,14 +12,22 @@ With `--gpus N > 1` and no torchrun environment, bench.py starts the N ranks its
 makes no GPU call).  `--dry-run` replaces the HIP model by a CPU stand-in on gloo, to test the launch plumbing without
 a GPU.  Rank 0 prints ONE JSON line.
 
-Live roofline: HIP events on the compute stream bracket every hot launch of the last timed step, grouped into families
-(forward / dgrad / wgrad GEMMs, attention fwd/bwd, LayerNorm fwd/bwd), each launch carrying its algorithmic FLOPs and
-HBM bytes.  `roofline` reports the family that takes the most time; `roofline_families`
-reports all of them.  `traffic` is the measured HBM bytes per launch of that family (rocprofv3 PMC passes under
-profiles/ for this exact workload), or null when no such profile exists.
-`cpu_baseline` times the repo's own host training step (train.py `time_steps`, VisionTransformer/_cpu.py) on all the
-cores this process may use: BASELINE config 1 exactly (ViT-Tiny/16 64^2 B8 fp32, 5 warmup + 30 steps) and a bounded
-ViT-Base/16 224^2 fp32 sample whose images/s is `value`.
+A plain run sets up, warms up, times the K steps, writes its outputs when `--dump-outputs DIR` is given and prints the
+result line; everything below is measured only with `--full`.  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (logits, loss, per-tensor gradient and parameter norms and a fixed, seeded sample of the
+gradients and of the updated parameters); the inputs, the initial weights and the dropout seeds are the same from run
+to run, so two builds can be compared output for output.  `--steps-ahead N` (default 8; 0: no bound) is how many steps
+the host may enqueue beyond the one the GPU runs: every step in flight holds its activations, and an unbounded host
+fills the HBM some fifty steps into a ViT-Base run (profiles/bench_steps_ahead_ab.log).
+
+Live roofline (`--full`): HIP events on the compute stream bracket every hot launch of the last timed step, grouped
+into families (forward / dgrad / wgrad GEMMs, attention fwd/bwd, LayerNorm fwd/bwd), each launch carrying its
+algorithmic FLOPs and HBM bytes.  `roofline` reports the family that takes the most
+time; `roofline_families` reports all of them.  `traffic` is the measured HBM bytes per launch of that family
+(rocprofv3 PMC passes under profiles/ for this exact workload), or null when no such profile exists.
+`cpu_baseline` (`--full`) times the repo's own host training step (train.py `time_steps`, VisionTransformer/_cpu.py)
+on all the cores this process may use: BASELINE config 1 exactly (ViT-Tiny/16 64^2 B8 fp32, 5 warmup + 30 steps) and
+a bounded ViT-Base/16 224^2 fp32 sample whose images/s is `value`.
 """
 import argparse
 import json
@@ -241,6 +249,45 @@ class FamilyTimer:
         return out
 
 
+STEPS_AHEAD_DEFAULT = 8
+DUMP_SAMPLE = 4096     # elements kept per parameter tensor: ViT-Base's 562 tensors -> 8 MB per sampled array
+
+
+def dump_outputs(path, logits, loss, model):
+    """What the last timed step handed its caller, as <path>/<name>.npy: the logits and the loss (float32, whole),
+    and of every parameter, in named_parameters() order, the L2 norm of its gradient and of its updated value
+    (float64, over every element) plus the same DUMP_SAMPLE seeded positions of both (float32, concatenated; a whole
+    tensor when it is smaller).  ViT-Base's gradients alone are 344 MB; this is 17 MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"logits": logits.detach().float().cpu().numpy(), "loss": loss.detach().float().reshape(1).cpu().numpy()}
+    if model is not None:
+        gen = torch.Generator().manual_seed(4321)
+        gn, pn, gs, ps = [], [], [], []
+        for name, p in model.named_parameters():
+            if p.grad is None:
+                raise RuntimeError(f"--dump-outputs: {name} has no gradient after the last timed step")
+            g, w = p.grad.detach().reshape(-1), p.detach().reshape(-1)
+            gn.append(g.double().norm())
+            pn.append(w.double().norm())
+            if g.numel() > DUMP_SAMPLE:
+                idx = torch.randint(0, g.numel(), (DUMP_SAMPLE,), generator=gen).to(g.device)
+                g, w = g[idx], w[idx]
+            gs.append(g.float())
+            ps.append(w.float())
+        out["grad_norms"] = torch.stack(gn).cpu().numpy()
+        out["param_norms"] = torch.stack(pn).cpu().numpy()
+        out["grad_sample"] = torch.cat(gs).cpu().numpy()
+        out["param_sample"] = torch.cat(ps).cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def dry_step(w):
+    """The compute of one --dry-run step (a module-level name, so a test can count the steps the loops run)."""
+    return (w @ w).sum()
+
+
 def run(args, rank, world, local):
     if args.dry_run:
         dev = torch.device("cpu")
@@ -259,12 +306,12 @@ def run(args, rank, world, local):
         comm_ms = [None]
 
         def step():
-            y = (w @ w).sum()
+            y = dry_step(w)
             if world > 1:
                 t = time.perf_counter()
                 dist.all_reduce(g)
                 comm_ms[0] = (time.perf_counter() - t) * 1e3      # the stand-in's all-reduce is fully exposed
-            return y
+            return y, y
         D = L = T = N = 0
         cfg = None
     else:
@@ -298,7 +345,7 @@ def run(args, rank, world, local):
             opt.zero_grad(set_to_none=True)
             loss.backward()
             opt.step()
-            return loss
+            return logits, loss
 
     def sync():
         if dev.type == "cuda":
@@ -306,30 +353,52 @@ def run(args, rank, world, local):
 
     if args.roctx and not args.dry_run:
         model.hip_engine.trace_ranges = True
-    log(f"rank {rank}/{world}: warmup {args.warmup} steps")
-    for _ in range(args.warmup):
-        loss = step()
-    sync()
-    log(f"rank {rank}/{world}: timing {args.steps} steps")
-    if world > 1:
-        dist.barrier()
-    sync()
-    # The live roofline brackets every hot launch of the LAST timed step with HIP events (each event record is a
-    # stream barrier: on every step they cost ~1.4 ms of the ~36 ms step, measured; on one step of K they cost ~1.4/K)
-    timer = FamilyTimer() if not args.dry_run and not args.no_roofline else None
+    # The host enqueues a step in about half the time the GPU needs to run it, so left alone it gets
+    # further ahead with every step, and every step in flight holds its own activations (the two-chain forward's
+    # buffers are recorded on the chain streams, so the allocator cannot hand them out again before those streams have
+    # passed the step that freed them): some fifteen steps ahead, about fifty steps into a run, ViT-B B256 fills the
+    # 288 GB HBM and a step fails.  --steps-ahead bounds that: before it enqueues another step the host waits for the
+    # step that many before the last one (profiles/bench_steps_ahead_ab.log: step time and reserved memory per bound).
+    marks = []
+
+    def pace():
+        if dev.type != "cuda" or args.steps_ahead <= 0:
+            return
+        ev = torch.cuda.Event()
+        ev.record()
+        marks.append(ev)
+        if len(marks) > args.steps_ahead:
+            marks.pop(0).synchronize()
+
+    timer = FamilyTimer() if args.full and not args.dry_run and not args.no_roofline else None
     roof_steps = 1 if timer is not None else 0
-    t0 = time.perf_counter()
     conc = None if args.dry_run else model.hip_engine.concurrent_wgrad
-    for i in range(args.steps):
-        if timer is not None and i == args.steps - roof_steps:
-            model.hip_engine.profile_hook = timer
-            # the event-bracketed step runs the in-order schedule: with the weight gradients on their side stream the
-            # backward families' events would time kernels sharing the GPU (the forward families are unaffected)
-            model.hip_engine.concurrent_wgrad = False
-        if world > 1 and not args.dry_run and i == args.steps - 1:
-            model.hip_engine.time_comm = True         # events around the bucket waits of the last step
-        loss = step()
-    sync()
+    try:
+        log(f"rank {rank}/{world}: warmup {args.warmup} steps")
+        for _ in range(args.warmup):
+            logits, loss = step()
+            pace()
+        sync()
+        log(f"rank {rank}/{world}: timing {args.steps} steps")
+        if world > 1:
+            dist.barrier()
+        sync()
+        # The live roofline brackets every hot launch of the LAST timed step with HIP events (each event record is a
+        # stream barrier: on every step they cost ~1.4 ms of the ~36 ms step, measured; on one step of K they cost
+        # ~1.4/K)
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            if timer is not None and i == args.steps - roof_steps:
+                model.hip_engine.profile_hook = timer
+                # the event-bracketed step runs the in-order schedule: with the weight gradients on their side stream
+                # the backward families' events would time kernels sharing the GPU (the forward families are unaffected)
+                model.hip_engine.concurrent_wgrad = False
+            if world > 1 and not args.dry_run and i == args.steps - 1:
+                model.hip_engine.time_comm = True         # events around the bucket waits of the last step
+            logits, loss = step()
+            pace()
+    finally:
+        sync()          # also when a step raised: nothing is torn down under kernels that are still queued
     if world > 1:
         dist.barrier()
     sync()
@@ -353,7 +422,11 @@ def run(args, rank, world, local):
         dist.all_reduce(ct, op=dist.ReduceOp.MAX)
         comm = float(ct.item()) if ct.item() >= 0 else None
     final_loss = float(loss.item())
-    log(f"rank {rank}/{world}: {elapsed / args.steps * 1e3:.2f} ms/step")
+    peak = f", peak reserved {torch.cuda.max_memory_reserved(dev) / 2 ** 30:.1f} GiB" if dev.type == "cuda" else ""
+    log(f"rank {rank}/{world}: {elapsed / args.steps * 1e3:.2f} ms/step{peak}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, logits, loss, None if args.dry_run else model)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -434,10 +507,10 @@ def run(args, rank, world, local):
                     v["hbm_frac_algorithmic"] = round(v["hbm_gbs_algorithmic"] * 1e9 / PEAK_HBM, 4)
                     del v["flop_per_step"], v["bytes_per_step"]
                 out["roofline_families"] = fams
-            if not args.no_gemm_peak:
+            if args.full and not args.no_gemm_peak:
                 log("measured GEMM peak")
                 out["measured_gemm_peak"] = gemm_peak(dev)
-        if world == 1 and not args.no_cpu_baseline and not args.dry_run:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dry_run:
             out["cpu_baseline"] = cpu_baseline(args.img, args.classes)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -488,9 +561,18 @@ def main(argv=None):
     ap.add_argument("--launch-mode", default="auto", choices=["auto", "shared", "persistent"],
                     help="N > 1: backward kernels beside RCCL as persistent one-per-CU grids (persistent; auto) or "
                          "one workgroup per item (shared) (DESIGN.md 5.4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gemm-peak", action="store_true", help="skip the measured 8192^3 GEMM peak (profiling runs)")
-    ap.add_argument("--no-roofline", action="store_true", help="no per-launch HIP events (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--steps-ahead", type=int, default=STEPS_AHEAD_DEFAULT, metavar="N",
+                    help="steps the host may enqueue ahead of the GPU (bounds the activations in flight); 0: no bound")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the live roofline of the last timed "
+                         "step, the measured GEMM peak and the CPU baseline (each has a --no-... switch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-gemm-peak", action="store_true",
+                    help="with --full: skip the measured 8192^3 GEMM peak (profiling runs)")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: no per-launch HIP events (profiling runs)")
     ap.add_argument("--roctx", action="store_true",
                     help="roctx ranges per kernel family (rocprofv3 --marker-trace timelines; costs host time)")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo stand-in step: tests rank launch without a GPU")
@@ -499,6 +581,8 @@ def main(argv=None):
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="library launch option (vit_set_option; A/B runs of kernel variants, default: shipped)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" in os.environ:           # launched by torchrun: one rank per process
         world = int(os.environ["WORLD_SIZE"])

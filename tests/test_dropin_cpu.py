@@ -176,6 +176,43 @@ def test_bench_spawns_ranks_dry_run():
     assert out["grad_comm_dtype"] == "fp32"
 
 
+def test_bench_plain_run_and_dump_outputs_dry_run(tmp_path, capsys, monkeypatch):
+    """A plain `bench.py` run times exactly --steps steps and measures nothing that only --full asks for;
+    `--dump-outputs DIR` writes the last timed step's outputs as float32 / float64 .npy files."""
+    import numpy as np
+    import bench
+    calls, times = [], []
+    real_step, real_clock = bench.dry_step, bench.time.perf_counter
+
+    def counted_step(w):
+        calls.append(len(times))                    # how many clock readings came before this step
+        return real_step(w)
+
+    def clock():
+        times.append(real_clock())
+        return times[-1]
+
+    monkeypatch.setattr(bench, "dry_step", counted_step)
+    monkeypatch.setattr(bench.time, "perf_counter", clock)
+    bench.main(["--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "d")])
+    # 1 warmup step before the clock starts, then exactly 3 steps between its two readings
+    assert calls == [0, 1, 1, 1] and len(times) == 2
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "images/s"
+    assert out["ms_per_step"] == round((times[1] - times[0]) / 3 * 1e3, 3)
+    assert out["higher_is_better"] is True and out["dtype"] == "bf16" and out["metric"]
+    assert not {"roofline", "roofline_families", "measured_gemm_peak", "cpu_baseline"} & set(out)
+    files = sorted(os.listdir(tmp_path / "d"))
+    assert files == ["logits.npy", "loss.npy"]
+    for f in files:
+        a = np.load(tmp_path / "d" / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+    with pytest.raises(SystemExit):
+        bench.main(["--dry-run", "--steps", "0"])
+
+
 def test_library_exports_every_header_symbol():
     hdr = open(os.path.join(ROOT, "include", "vit_hip.h")).read()
     declared = set(re.findall(r"^\s*(?:int|int64_t|const char\*)\s+(vit_\w+)\s*\(", hdr, re.M))

@@ -28,9 +28,9 @@ for s in $STEPS; do
             VIT_HIP_LIB=tools/variants/libvit_hip_$v.so timeout -k 10 120 python -u tools/ln_bench.py > "$OUT/ln_$v.log" 2>&1 || break
           done ;;
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 ;;
-    bench) timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+    bench) timeout -k 10 600 python bench.py --full >"$OUT/bench.json" 2> "$OUT/bench.err" ;;
     prof) timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-            python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/prof.log" 2>&1 ;;
+            python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/prof.log" 2>&1 ;;
     *) echo "unknown step $s"; continue ;;
   esac
   rc=$?

@@ -9,10 +9,10 @@ OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 export TMPDIR=/tmp
 KEY=${PMC_KEY:-base_224_b256_bf16}
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-  python bench.py --steps 10 --warmup 3 --no-cpu-baseline $EXTRA > "$OUT/prof.json" 2> "$OUT/prof.err" || {
+  python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline $EXTRA > "$OUT/prof.json" 2> "$OUT/prof.err" || {
   echo "kernel-trace run failed"; exit 1; }
 S=$(find "$OUT/prof" -name "*kernel_stats.csv" | head -1)
-python tools/prof_summary.py "$S" 13 "rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline $EXTRA" > "$OUT/stats.md"
+python tools/prof_summary.py "$S" 13 "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline $EXTRA" > "$OUT/stats.md"
 cp "$S" "$OUT/kernel_stats.csv"
 # PMC passes under the schedule bench.py's event-bracketed roofline step times (round 6): in order,
 # one forward chain and the weight gradients on the compute stream, so per-family counters and the live per-launch

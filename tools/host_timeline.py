@@ -4,7 +4,8 @@ had already drained its queue when the host got there (then the GPU idles on the
 For each timed step: host milliseconds spent in model(x), cross_entropy, zero_grad, loss.backward and opt.step, and — via
 an event recorded on the compute stream at each phase boundary and queried right away — whether the GPU had already
 finished everything enqueued before that point ("drained"), plus the GPU time from step start to each boundary.
-Steps run back to back as in bench.py (one synchronization at the end).
+Steps run back to back with one synchronization at the end (bench.py's loop besides bounds how far the host may get
+ahead, --steps-ahead; over the few steps timed here that bound is not reached).
 usage: python tools/host_timeline.py [--steps 10] [--engine ATTR=INT ...]
 """
 import argparse
