@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VIT_ABI_VERSION 14
+#define VIT_ABI_VERSION 15
 
 typedef enum { VIT_OK = 0, VIT_ERR_INVALID = 1, VIT_ERR_LAUNCH = 2 } vit_status;
 typedef enum { VIT_F32 = 0, VIT_BF16 = 1, VIT_MASK4 = 2 } vit_dtype;
@@ -58,18 +58,19 @@ const char* vit_last_error(void);
  *   "gemm_group_m"       0 (automatic): tile-row group size of the 256x256 tile order
  *   "gemm_epi_general"   0: 1 forces the general (unspecialised) GEMM epilogue
  *   "gemm_persist"       1: persistent one-workgroup-per-CU grid for the wide-epilogue GEMM kinds (0: one per tile)
- *   "attn_fwd_split"     0: 1 forces the tiled attention forward for T <= 256
+ *   "attn_fwd_split"     0: 1 forces the tiled attention forward for T <= 256 (default there: the persistent ring)
  *   "attn_bwd_split"     0: 1 forces the tiled attention backward for T <= 256
  *   "attn_bwd_grid"      0 (automatic): workgroups of the persistent attention backward
  *   "ln16"               1: the 16-B-per-lane LayerNorm forward where the layout allows it
  *   "ln_al"              1: LayerNorm backward accumulators in LDS (0: registers)
- *   "attn_fwd_ring"      1: the persistent ring attention forward for T <= 256 (0: one workgroup per (image, head))
  *   "gemm_tail_v2"       0: 1 runs the tile rows of a last round of 256x256 tiles at most half full that the split-K
  *                        tail does not take as 128x128 tiles (two workgroups per CU) in a second launch (measured
  *                        slower at C2: 33.0 vs 31.6 ms/step)
  *   "splitk_rounds"      1: rounds of 256 workgroups the weight-gradient K split aims at (vit_gemm_split_k_hint)
  *   "attn_fwd_grid"      0 (automatic: one workgroup per CU): workgroups of the persistent ring attention forward
  *                        when the call's own max_wgs is 0
+ * ABI 15 removed the one-workgroup-per-head attention forward, which lost its A/B runs, together with the option name
+ * that selected it: vit_set_option refuses that name.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);

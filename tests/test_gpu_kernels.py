@@ -472,11 +472,10 @@ def _attn_ref(qkv, B, T, H, hd, scale):
 @pytest.mark.parametrize("shape", ["proj_fwd", "fc2_fwd", "dgrad_qkv", "fc1_fwd", "dgrad_fc2m", "dgrad_proj"])
 def test_gemm_c2_shapes_tail_split(libopt, shape):
     """The forward / input-gradient GEMMs at their real C2 shapes (M = 50,432: 591 / 2,364 tiles over 256 CUs, the
-    persistent grid).  With the tails of a last partial round — the split-K tail (option gemm_tail: N = 768 and
-    K >= 2048 run it split over K with fp32 slabs) and the 128x128-tile tail (option gemm_tail_v2: the K = 768 shapes
-    run its tile rows as quarter tiles, two workgroups per CU; round 5) — against whole 256x256 tiles only: the same
-    outputs to bf16 rounding of a different fp32 summation order, identical keep / ReLU bits where the pre-rounding
-    values agree, bitwise run to run, and within bf16 tolerance of an fp32 torch product."""
+    persistent grid).  With the split-K tail of a last partial round (option gemm_tail: N = 768 and K >= 2048 run it
+    split over K with fp32 slabs) against whole 256x256 tiles only: the same outputs to bf16 rounding of a different
+    fp32 summation order, identical keep / ReLU bits where the pre-rounding values agree, bitwise run to run, and
+    within bf16 tolerance of an fp32 torch product."""
     M, D = 256 * 197, 768
     libopt("gemm_tail", 1)                          # off by default since round 5 (the two-stream schedule)
     libopt("gemm_tail_min_kt", 32)                  # the QKV input gradient's tail too (K = 2304: 36 k-tiles)
@@ -505,7 +504,6 @@ def test_gemm_c2_shapes_tail_split(libopt, shape):
     c1b, m1b = run()
     assert torch.equal(c1, c1b) and torch.equal(m1, m1b)                 # deterministic
     libopt("gemm_tail", 0)
-    libopt("gemm_tail_v2", 0)
     c0, m0 = run()
     ref = a.float() @ (b.float().t() if bkc else b.float())
     scale = float(ref.abs().max())
@@ -682,9 +680,9 @@ def test_attention_bwd_shared_cus_bitwise(libopt, grid):
 def test_attention_fwd_ring_ragged_grids(libopt, T):
     """The persistent ring forward (attn_fwd_ring<NT>) where workgroups take several items and the item count is not a
     multiple of the grid: B = 17, H = 12 (204 items) over 64 and 192 workgroups (per call, max_wgs)
-    and over the option attn_fwd_grid; T = 197 is the 3-slot ring (NT 13), T = 209 / 240 / 256 the 2-slot ring (NT
-    14-16).  Against fp64 on the same bf16 inputs (o to 2e-2 of the largest value, lse to 1e-3), bitwise equal over
-    every grid (items are independent), and within the same gate of the one-workgroup-per-item forward."""
+    and over the option attn_fwd_grid; T = 197 is the ring with the Q double buffer (NT 13), T = 209 / 240 / 256 the
+    ring with Q in the K image (NT 14-16).  Against fp64 on the same bf16 inputs (o to 2e-2 of the largest value, lse
+    to 1e-3), bitwise equal over every grid (items are independent), and within the same gate of the tiled forward."""
     torch.manual_seed(T)
     B, H, hd = 17, 12, 64
     D = H * hd
@@ -709,7 +707,7 @@ def test_attention_fwd_ring_ragged_grids(libopt, T):
     for o, lse in outs[1:]:
         assert torch.equal(o, outs[0][0]) and torch.equal(lse, outs[0][1])
     libopt("attn_fwd_grid", 0)
-    libopt("attn_fwd_ring", 0)
+    libopt("attn_fwd_split", 1)
     of, lf = _ops.attn_fwd(qkv, B, T, H, hd, 8.0)
     assert float((of.double() - outs[0][0].double()).abs().max()) <= 2e-2 * scale_o
     assert float((lf - outs[0][1]).abs().max()) <= 1e-3 * max(1.0, float(lse_ref.abs().max()))
@@ -717,7 +715,7 @@ def test_attention_fwd_ring_ragged_grids(libopt, T):
 
 @pytest.mark.parametrize("T", [1, 31, 32, 33, 197, 256])
 def test_attention_fwd_fused_matches_split(libopt, T):
-    """The one-workgroup-per-(image, head) forward (T <= 256) against the 128-query-tile kernel and fp32."""
+    """The default forward for T <= 256 (the persistent ring) against the 128-query-tile kernel and fp32."""
     torch.manual_seed(T + 1)
     B, H, hd = 2, 3, 64
     qkv = (torch.randn(B * T, 3 * H * hd, device=DEV) * 0.5).bfloat16()

@@ -15,6 +15,6 @@ for v in "$@"; do
     VIT_HIP_LIB=$LIB timeout -s KILL 120 rocprofv3 --pmc $grp -d "$OUT/$v/p$i" -o run --output-format csv -- \
       python tools/attn_bench.py --reps 3 > "$OUT/$v/p$i.log" 2>&1 || { echo "pmc $v pass $i failed"; exit 1; }
   done
-  python tools/kernel_pmc.py "attn_bwd_fused|attn_delta|attn_fwd_fused" "$OUT/$v/p1" "$OUT/$v/p2" > "$OUT/pmc_$v.txt"
+  python tools/kernel_pmc.py "attn_bwd_fused|attn_delta|attn_fwd_ring" "$OUT/$v/p1" "$OUT/$v/p2" > "$OUT/pmc_$v.txt"
   rm -rf "$OUT/$v/p1" "$OUT/$v/p2"
 done

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Interleaved whole-step A/B of runtime switches: usage bash tools/bench_ab.sh TAG ROUNDS "ARGS_A" "ARGS_B" ...
-# (extra bench.py arguments, e.g. "--engine row0_attention=0" or "--opt attn_fwd_ring=0"; "-" = none).  Each run: bench.py, 20 steps, no CPU leg / GEMM peak / per-launch events.
+# (extra bench.py arguments, e.g. "--engine row0_attention=0" or "--opt attn_fwd_split=1"; "-" = none).  Each run: bench.py, 20 steps, no CPU leg / GEMM peak / per-launch events.
 TAG=$1; R=$2; shift 2
 OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 for r in $(seq 1 "$R"); do

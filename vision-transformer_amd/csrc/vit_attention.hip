@@ -168,32 +168,10 @@ VIT_DEV s16x4 tr_read(const bf16_t* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr_t)p);
 }
 
-// Stage a 64-row x 64-col bf16 tile (rows r0.., columns col0..col0+63 of a row-major matrix with leading dim ld,
-// rows >= nrows zero-filled) through registers.
-VIT_DEV void tile_load(const bf16_t* __restrict__ src, int64_t ld, int64_t r0, int64_t nrows, int64_t col0, int tid,
-                       uint4 (&reg)[2]) {
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int q = tid + 256 * it;
-    const int64_t r = r0 + (q >> 3);
-    const int c = q & 7;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (r < nrows) v = *reinterpret_cast<const uint4*>(src + r * ld + col0 + c * 8);
-    reg[it] = v;
-  }
-}
-VIT_DEV void tile_store(bf16_t* lds, int tid, const uint4 (&reg)[2]) {
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int q = tid + 256 * it;
-    const int r = q >> 3, c = q & 7;
-    *reinterpret_cast<uint4*>(lds + r * HD + ((c ^ aswz(r)) << 3)) = reg[it];
-  }
-}
-
-// The same 64-row tile by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write): 8 pieces of 8 rows,
-// wave w of the 4 issues pieces 2w and 2w + 1, lane-linear destination with the chunk swizzle applied to the source
-// address (the layout tile_store writes; aswz(r) = aswz(r mod 64)).  Rows >= nrows are clamped to nrows - 1: finite
+// Stage a 64-row x 64-col bf16 tile (rows r0.., columns col0..col0+63 of a row-major matrix with leading dim ld) by
+// LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write): 8 pieces of 8 rows, wave w of the 4 issues
+// pieces 2w and 2w + 1, lane-linear destination with the chunk swizzle applied to the source address (row r's 16-B
+// chunk c lands at chunk c ^ aswz(r); aswz(r) = aswz(r mod 64)).  Rows >= nrows are clamped to nrows - 1: finite
 // data, and every caller masks those rows (keys: S = -inf or dS = 0; queries: lse = +inf).  Issued as inline asm so
 // the compiler's waitcnt pass does not drain it at the LDS reads of the other buffer; the caller retires it with
 // tile_wait() before the barrier that publishes the buffer.
@@ -296,13 +274,10 @@ VIT_DEV void store_block_rows16(const f32x16 (&acc)[2], float mul, bf16_t* row, 
 // head's whole K / V (or Q / dO), so in launch order they sat on nblk different XCDs and each fetched the head slice
 // from beyond L2 (C5 PMC: 3.5-3.7x the algorithmic bytes).  Bijective remap: XCD x runs a contiguous range of logical
 // tiles, tile j = (head j / nblk, block j % nblk), so a head's blocks share one L2 and run at about the same time.
-#ifndef ATT_XCD                  // A/B builds only: 0 = launch order
-#define ATT_XCD 1
-#endif
 VIT_DEV void xcd_block(int64_t nblk, int64_t& blk, int64_t& bh) {
   const int64_t orig = blockIdx.x, nwg = gridDim.x;
   const int64_t xcd = orig % 8, q = nwg / 8, rr = nwg % 8;
-  const int64_t j = ATT_XCD ? (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8 : orig;
+  const int64_t j = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
   bh = j / nblk;
   blk = j - bh * nblk;
 }
@@ -407,14 +382,12 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma(const bf16_t* __restrict
 // C5).  With the forward's fp32 O (o32) delta is exact to fp32: under the reference's x sqrt(hd) scaling most softmax
 // rows are saturated, where dS = P (dP - delta) is a tiny difference and delta from the bf16-rounded O swamps it
 // (measured: the Q / K weight gradients of a saturated head 10x off the bf16-rounding oracle).
-#ifndef ATT_DQ_MINB              // A/B builds only: workgroups per CU the dQ kernel's register budget is sized for
-#define ATT_DQ_MINB 2
-#endif
 template <class TO>
-__global__ __launch_bounds__(256, ATT_DQ_MINB) void attn_bwd_dq_mfma(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_o,
-                                                        const TO* __restrict__ o, const float* __restrict__ lse,
-                                                        float* __restrict__ delta, bf16_t* __restrict__ dqkv,
-                                                        int64_t Tn, int64_t H, float scale) {
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_mfma(const bf16_t* __restrict__ qkv,
+                                                           const bf16_t* __restrict__ d_o, const TO* __restrict__ o,
+                                                           const float* __restrict__ lse, float* __restrict__ delta,
+                                                           bf16_t* __restrict__ dqkv, int64_t Tn, int64_t H,
+                                                           float scale) {
   __shared__ __attribute__((aligned(16))) bf16_t smem[2 * 2 * TILE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5;
   int64_t blk, bh;
@@ -502,14 +475,12 @@ __global__ __launch_bounds__(256, ATT_DQ_MINB) void attn_bwd_dq_mfma(const bf16_
   store_block_rows16(dq, scale, dqkv + (b * Tn + (q < Tn ? q : Tn - 1)) * ld + h * HD + 8 * hf, q < Tn);
 }
 
-#ifndef ATT_DKDV_MINB            // A/B builds only: workgroups per CU the dK / dV kernel is sized for
-#define ATT_DKDV_MINB 3
-#endif
-__global__ __launch_bounds__(256, ATT_DKDV_MINB) void attn_bwd_dkdv_mfma(const bf16_t* __restrict__ qkv,
-                                                          const bf16_t* __restrict__ d_o,
-                                                          const float* __restrict__ lse,
-                                                          const float* __restrict__ delta, bf16_t* __restrict__ dqkv,
-                                                          int64_t Tn, int64_t H, float scale) {
+__global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_mfma(const bf16_t* __restrict__ qkv,
+                                                             const bf16_t* __restrict__ d_o,
+                                                             const float* __restrict__ lse,
+                                                             const float* __restrict__ delta,
+                                                             bf16_t* __restrict__ dqkv, int64_t Tn, int64_t H,
+                                                             float scale) {
   __shared__ __attribute__((aligned(16))) bf16_t smem[2 * 2 * TILE];  // [buf][Q, dO]
   // [buf][-lse / scale, -delta] per query: the initial S / dP accumulators (rows >= T: -inf -> P = 0)
   __shared__ __attribute__((aligned(16))) float stat[2][2][KT];
@@ -614,60 +585,13 @@ __global__ __launch_bounds__(256, ATT_DKDV_MINB) void attn_bwd_dkdv_mfma(const b
 // Fused backward for T <= 256 (ViT: T = 197): one 8-wave workgroup per (image, head), everything from LDS.
 //   LDS: K, Q, dO (and V when it fits) as [Tp][64] images (Tp = T rounded up to 32), lse2 per query, the delta
 //   partials, a double-buffered dS^T image [Tp keys][32 queries] and a double-buffered dQ staging block.
-//   Wave w owns key block w (32 keys: its K / V fragments live in registers, dK / dV accumulate in registers) and
-//   walks the query blocks qb:  S, dP (keys on lanes) -> P -> dV += dO^T P, delta = rowsum(P * dP) over the key
-//   waves, dS = P (dP - delta) -> dK += Q^T dS, dS^T -> LDS; then dQ[qb] (32 x 64) is split over the 8 waves as
-//   16x16 tiles (16x16x32 MFMA over all Tp keys): no recomputation of P, no atomics — deterministic.
+//   Wave w owns key block w (32 keys: its K / V fragments are re-read from the LDS images, V's held in registers when
+//   V has no image; dK / dV accumulate in registers) and walks the query blocks qb:  S, dP (keys on lanes) -> P ->
+//   dV += dO^T P, delta = rowsum(P * dP) over the key waves, dS = P (dP - delta) -> dK += Q^T dS, dS^T -> LDS; then
+//   dQ[qb] (32 x 64) is split over the 8 waves as 16x16 tiles (16x16x32 MFMA over all Tp keys): no recomputation of
+//   P, no atomics — deterministic.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int FB_TMAX = 256;
-#ifndef ATT_DWAV
-#define ATT_DWAV 1
-#endif
-#ifndef ATT_KVLDS
-#define ATT_KVLDS 1
-#endif
-#ifndef ATT_ORDER                // A/B builds only: loop-body order (0 back, front, dq; 1 front, back, dq; 2 dq first;
-                                 // 3 waves 4-7 dq first)
-#define ATT_ORDER 0
-#endif
-#ifndef ATT_PRIO                 // A/B builds only: s_setprio 1 around the S / dP MFMA chain
-#define ATT_PRIO 0
-#endif
-
-
-VIT_DEV __amdgpu_buffer_rsrc_t make_rsrc_b(const void* base, int64_t bytes) {
-  const uint32_t nrec = bytes >= 0x7fffffffLL ? 0x7fffffffu : (uint32_t)bytes;
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
-
-// A operand (16x16x32) of X^T from a [row][64] image: lane holds X[r0 + 8(lane>>4) + j][c0 + (lane&15)] for
-// j = 0..7, via two transposed reads (rows +0..3, +4..7).  `rowlen` = elements per image row; `swz` = chunk swizzle.
-template <int ROWLEN, bool ASWZ>
-VIT_DEV bf16x8_t col_frag16(const bf16_t* img, int r0, int c0, int lane) {
-  const int g = lane >> 4, lg = lane & 15, q = lg >> 2, p = lg & 3;
-  const int col = c0 + 4 * p;
-  const int c = col >> 3;
-  const int ra = r0 + 8 * g + q, rb = ra + 4;
-  const int ca = ASWZ ? (c ^ aswz(ra)) : c, cb = ASWZ ? (c ^ aswz(rb)) : c;
-  s16x4 lo = tr_read(img + ra * ROWLEN + (ca << 3) + (col & 7));
-  s16x4 hi = tr_read(img + rb * ROWLEN + (cb << 3) + (col & 7));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
-// LDS-DMA of one [Tp][64] head slice (rows of a row-major matrix with leading dim ld, columns col0..col0+63)
-// into a swizzled [Tp][64] image: 1 KiB pieces of 8 rows, lane-linear destination, the chunk swizzle applied to
-// the source address; rows >= Tn are zero-filled by an out-of-range offset.
-VIT_DEV void dma_head_slice(__amdgpu_buffer_rsrc_t rs, int64_t row0, int64_t ld, int64_t col0, int Tn, int Tp,
-                            bf16_t* img, int wave, int lane, int nwaves = 8) {
-  for (int pc = wave; pc < Tp / 8; pc += nwaves) {
-    const int r = pc * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ aswz(r);
-    const uint32_t off = r < Tn ? (uint32_t)(2 * ((row0 + r) * ld + col0 + c * 8)) : 0x80000000u;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(img + pc * 512), 16, off,
-                                             0, 0, 0);
-  }
-}
 
 // Row-contiguous store of a [rows][64] bf16 LDS image (row stride RS elements, no swizzle) to global rows (row stride
 // ld): 8 lanes per 128-B row.  Rows of a stride that is not a multiple of 8 elements (the padded dQ staging, 68) are
@@ -869,7 +793,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
       tf_off[db][1] = r2 * HD + ((c ^ aswz(r2)) << 3) + (pp & 1) * 4;
     }
   }
-  int cf_k[2], cf_s[2];                                // col_frag16 on K (dQ A operand) and on dS^T (B operand)
+  int cf_k[2], cf_s[2];                                // transposed 16x16x32 reads: K (dQ A operand), dS^T (B operand)
   {
     const int g = lane >> 4, lg = lane & 15, q = lg >> 2, pp = lg & 3;
     const int ra = 8 * g + q, rb2 = ra + 4;
@@ -921,13 +845,10 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
     }
     __syncthreads();                                  // every wave's DMA landed
     ATT_ISTAMP(1);
-    bf16x8_t kf[4], vf[4];
+    bf16x8_t vf[4];                                   // V fragments from global when V has no LDS image
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (!ATT_KVLDS) kf[s] = row_frag(Ks, kb, s, lane);
-      if (!ATT_KVLDS || !VLDS)
-        vf[s] = VLDS ? row_frag(Vs, kb, s, lane) : glb_frag(qkv + b * Tn * ld, ld, kb, Tn, 2 * D + h * HD, s, lane);
-    }
+    for (int s = 0; s < 4; ++s)
+      if (!VLDS) vf[s] = glb_frag(qkv + b * Tn * ld, ld, kb, Tn, 2 * D + h * HD, s, lane);
     f32x16 dk[2] = {f32x16{}, f32x16{}}, dv[2] = {f32x16{}, f32x16{}};
     float pc[16], dpc[16];                            // P and dP of the block between front and back
 
@@ -940,16 +861,10 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
       f32x16 sacc = {}, pacc = {};
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-#if ATT_KVLDS
         const bf16x8_t kfs = rrd(Ks + kb * HD, rf_off[s]), vfs = VLDS ? rrd(Vs + kb * HD, rf_off[s]) : vf[s];
-#else
-        const bf16x8_t kfs = kf[s], vfs = vf[s];
-#endif
-        if (ATT_PRIO && s == 0) __builtin_amdgcn_s_setprio(1);
         sacc = mfma32(rrd(Qb, rf_off[s]), kfs, sacc);             // S[q][key]: lane = key
         pacc = mfma32(rrd(Gb, rf_off[s]), vfs, pacc);             // dP[q][key]
       }
-      if (ATT_PRIO) __builtin_amdgcn_s_setprio(0);
       // registers 4g..4g+3 <-> queries q0 + 8g + 4hf + 0..3: broadcast b128 reads of lse2
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -988,7 +903,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
       const int q0 = qb * 32;
       const bf16_t* Qb = Qs + q0 * HD;
       float ds[16];
-#if ATT_DWAV
       const float* dp = dpart + (qb & 1) * 256 + (lane & 31);
       float dsum = dp[0];
 #pragma unroll
@@ -1001,17 +915,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
 #pragma unroll
         for (int i = 0; i < 4; ++i) ds[4 * g + i] = pc[4 * g + i] * (dpc[4 * g + i] - dv4[i]);
       }
-#else
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float* dp = dpart + (qb & 1) * 256 + 8 * g + 4 * hf;
-        f32x4 dv4 = *reinterpret_cast<const f32x4*>(dp);
-#pragma unroll
-        for (int w = 1; w < nqb; ++w) dv4 += *reinterpret_cast<const f32x4*>(dp + w * 32);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ds[4 * g + i] = pc[4 * g + i] * (dpc[4 * g + i] - dv4[i]);
-      }
-#endif
       const bf16x8_t d0 = pack8(ds), d1 = pack8(ds + 8);
 #pragma unroll
       for (int db = 0; db < 2; ++db) {
@@ -1067,7 +970,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
       front(1);
       if (wave >= 4) prefetch(-1);                    // dO block 0
       load_lse(more ? nxt : item);                    // after front(0) consumed the V fragments: no wait on it
-      if (VLDS && !ATT_KVLDS) dma_slice_g(qkv, sb_ * Tn, ld, 2 * D + sh_ * HD, Tn, Tp, Vs, wave, lane);  // V: top only
       lds_barrier();
       ATT_ISTAMP(3);
       back(1);
@@ -1079,7 +981,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
 #pragma unroll 1
       for (int it = 3; it < nqb; ++it) {
         ATT_STAMP(it, 0);
-#if ATT_STAMPS
         dq_store(it - 3);
         ATT_STAMP(it, 1);
         back(it - 1);
@@ -1090,39 +991,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
         ATT_STAMP(it, 4);
         prefetch(it - 2);
         ATT_STAMP(it, 5);
-        lds_barrier();
-        continue;
-#endif
-#if ATT_ORDER == 1
-        dq_store(it - 3);
-        front(it);
-        back(it - 1);
-        dq(it - 2);
-#elif ATT_ORDER == 2
-        dq_store(it - 3);
-        dq(it - 2);
-        back(it - 1);
-        front(it);
-#elif ATT_ORDER == 3
-        // SIMD partners (waves w, w + 4) in different phases: waves 4-7 run the LDS / MFMA-heavy dQ tile first while
-        // waves 0-3 run the VALU-heavy delta / dS of back(); back stays before front (front overwrites P / dP)
-        dq_store(it - 3);
-        if (wave < 4) {
-          back(it - 1);
-          front(it);
-          dq(it - 2);
-        } else {
-          dq(it - 2);
-          back(it - 1);
-          front(it);
-        }
-#else
-        dq_store(it - 3);
-        back(it - 1);
-        front(it);
-        dq(it - 2);
-#endif
-        prefetch(it - 2);
         lds_barrier();                                // LDS only: the prefetch and the dQ stores stay in flight
       }
       ATT_ISTAMP(5);
@@ -1130,7 +998,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
       back(nqb - 1);
       dq(nqb - 2);
       prefetch(nqb - 2);                              // Q block nqb-2, dO block nqb-1
-      if (VLDS && ATT_KVLDS) dma_slice_g(qkv, sb_ * Tn, ld, 2 * D + sh_ * HD, Tn, Tp, Vs, wave, lane);  // V: fronts done
+      if (VLDS) dma_slice_g(qkv, sb_ * Tn, ld, 2 * D + sh_ * HD, Tn, Tp, Vs, wave, lane);  // V: fronts done
       lds_barrier();
       dq_store(nqb - 2);
       dq(nqb - 1);
@@ -1148,7 +1016,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
         if (it >= 2) dq(it - 2);
         if ((wave >= 4 && it >= 1 && it <= nqb) || (wave < 4 && it >= 2)) prefetch(it - 2);
         if (it == 1) load_lse(more ? nxt : item);
-        if (VLDS && it == (ATT_KVLDS ? nqb : 1)) dma_slice_g(qkv, sb_ * Tn, ld, 2 * D + sh_ * HD, Tn, Tp, Vs, wave, lane);
+        if (VLDS && it == nqb) dma_slice_g(qkv, sb_ * Tn, ld, 2 * D + sh_ * HD, Tn, Tp, Vs, wave, lane);
         lds_barrier();
       }
       dq_store(nqb - 1);
@@ -1186,136 +1054,18 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused(const bf16_t* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Fused forward for T <= 256 (ViT: T = 197): one workgroup per (image, head) with NKB = Tp/32 waves (Tp = T rounded up
-// to 32).  K and V of the head are LDS-DMA'd once into swizzled [Tp][64] images (rows >= T zero-filled); wave w owns
-// queries 32w..32w+31 (Q fragments straight from global) and walks the NKB key blocks with the online softmax of
-// attn_fwd_mfma (S^T = K Q^T: one query per lane column; P^T reused in registers as the B operand of O^T = V^T P^T).
-// Against attn_fwd_mfma (128-query workgroups over 64-key tiles) no all-padding query or key block is computed
-// (T = 197: 7 x 7 blocks of 32 instead of 8 x 8) and K/V leave HBM once per (image, head); at <= 64 KiB of LDS two
-// workgroups share a CU, so one's DMA prologue overlaps the other's loop.  O leaves registers as 16-B row pieces: a
-// permlane32 half swap pairs the two 8-B column groups a row is split over (cdna_hip_programming.md T21).
-// ---------------------------------------------------------------------------------------------------------------
-// One wave's 32 queries (q0 = 32 * wave) of one (image, head) against the NKB key blocks of the K / V images: the
-// online softmax of attn_fwd_mfma, then O (bf16, 16-B row pieces), optionally O unrounded (o32) and the LSE.
-template <int NKB>
-VIT_DEV void fwd_queries(const bf16_t* Ks, const bf16_t* Vs, const bf16x8_t (&qf)[4], int wave, int lane, int Tn,
-                         float c2, bf16_t* __restrict__ o, float* __restrict__ o32, float* __restrict__ lse, int64_t b,
-                         int64_t h, int64_t bh, int64_t D) {
-  constexpr int Tp = NKB * 32;
-  const int hf = lane >> 5;
-  const int q0 = wave * 32;
-  f32x16 oacc[2] = {f32x16{}, f32x16{}};
-  float m_run = -INFINITY, l_run = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < Tp; kb += 32) {
-    f32x16 sacc = {};
-#pragma unroll
-    for (int s = 0; s < 4; ++s) sacc = mfma32(row_frag(Ks, kb, s, lane), qf[s], sacc);
-    float x[16];
-    float mloc = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      x[r] = kb + acc_row(r, hf) < Tn ? sacc[r] * c2 : -INFINITY;
-      mloc = fmaxf(mloc, x[r]);
-    }
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-    const float m_new = fmaxf(m_run, mloc);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      x[r] = __builtin_amdgcn_exp2f(x[r] - m_new);
-      psum += x[r];
-    }
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
-    oacc[0] *= alpha;
-    oacc[1] *= alpha;
-    const bf16x8_t pb0 = pack8(x), pb1 = pack8(x + 8);
-#pragma unroll
-    for (int db = 0; db < 2; ++db) {
-      oacc[db] = mfma32(tr_frag(Vs, kb, db, lane), pb0, oacc[db]);
-      oacc[db] = mfma32(tr_frag(Vs, kb + 16, db, lane), pb1, oacc[db]);
-    }
-  }
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l_tot;
-  const int q = q0 + (lane & 31);
-  if (o32 && q < Tn) {                               // fp32 O for the tiled backward's delta
-    float* orow32 = o32 + (b * Tn + q) * D + h * HD + 4 * hf;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float v[4] = {oacc[db][4 * g] * inv, oacc[db][4 * g + 1] * inv, oacc[db][4 * g + 2] * inv,
-                            oacc[db][4 * g + 3] * inv};
-        st4<float>(orow32 + db * 32 + 8 * g, v);
-      }
-  }
-  // lane (q, hf) holds O[q][8k + 4hf .. 8k + 4hf + 3] in group k = 4db + g; one permlane32 swap per dword pairs groups
-  // (k, k+1) into 16 contiguous bytes per lane: columns 8k..8k+7 on lanes < 32, 8k+8..8k+15 on lanes >= 32
-  uint32_t pk[8][2];
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int k = 4 * db + g;
-      pk[k][0] = (uint32_t)f2bf(oacc[db][4 * g] * inv) | ((uint32_t)f2bf(oacc[db][4 * g + 1] * inv) << 16);
-      pk[k][1] = (uint32_t)f2bf(oacc[db][4 * g + 2] * inv) | ((uint32_t)f2bf(oacc[db][4 * g + 3] * inv) << 16);
-    }
-  bf16_t* orow = o + (b * Tn + q) * D + h * HD + 8 * hf;
-#pragma unroll
-  for (int k = 0; k < 8; k += 2) {
-#pragma unroll
-    for (int w2 = 0; w2 < 2; ++w2) {
-      const auto sw = __builtin_amdgcn_permlane32_swap(pk[k][w2], pk[k + 1][w2], false, false);
-      pk[k][w2] = sw[0];
-      pk[k + 1][w2] = sw[1];
-    }
-    if (q < Tn) *reinterpret_cast<uint4*>(orow + 8 * k) = make_uint4(pk[k][0], pk[k][1], pk[k + 1][0], pk[k + 1][1]);
-  }
-  if (q < Tn && hf == 0) lse[bh * Tn + q] = (m_run + log2f(l_tot)) / LOG2E;
-}
-
-template <int NKB>
-__global__ __launch_bounds__(NKB * 64) void attn_fwd_fused(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
-                                                           float* __restrict__ o32, float* __restrict__ lse,
-                                                           int64_t Tn64, int64_t H, float scale) {
-  constexpr int Tp = NKB * 32;
-  __shared__ __attribute__((aligned(16))) bf16_t smem[2 * Tp * HD];
-  bf16_t* Ks = smem;
-  bf16_t* Vs = smem + Tp * HD;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int Tn = (int)Tn64;
-  const int64_t bh = blockIdx.x, b = bh / H, h = bh % H;
-  const int64_t D = H * HD, ld = 3 * D;
-  {
-    const int64_t nb = gridDim.x / H;                  // host guarantees the tensor is < 2 GiB
-    const __amdgpu_buffer_rsrc_t rq = make_rsrc_b(qkv, nb * Tn * ld * 2);
-    dma_head_slice(rq, b * Tn, ld, D + h * HD, Tn, Tp, Ks, wave, lane, NKB);
-    dma_head_slice(rq, b * Tn, ld, 2 * D + h * HD, Tn, Tp, Vs, wave, lane, NKB);
-  }
-  bf16x8_t qf[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) qf[s] = glb_frag(qkv + b * Tn * ld, ld, wave * 32, Tn, h * HD, s, lane);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  fwd_queries<NKB>(Ks, Vs, qf, wave, lane, Tn, scale * LOG2E, o, o32, lse, b, h, bh, D);
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
 // Ring forward for T <= 256 (round 5; ViT: T = 197): persistent, one workgroup of NT = ceil(T/16) waves per CU, wave w
 // owning queries 16w .. 16w + 15 of every (image, head) item the workgroup takes (items g, g + grid, ...).
-//   * K and V of an item are LDS-DMA'd into a [Tp][64] image pair (Tp = 16 NT: 208 rows at T = 197, 53 KB) of a ring of
-//     NS slots (3 while they fit in the 160 KiB: the item two ahead streams in while this one computes; 2 above
-//     T = 208).  Each wave issues 4 of the item's 4 NT pieces, so HBM sees a continuous stream instead of the burst at
-//     the start of every one-item workgroup.
-//   * Q of the next item is LDS-DMA'd into the K image of the current slot once every wave is past its S products
-//     (2 pieces per wave), and read as MFMA fragments after the next item's first barrier.  Every global load is
-//     LDS-DMA, so the counted `s_waitcnt vmcnt` at the top of an item retires exactly this item's K / V / Q pieces and
-//     leaves the ring's next K / V in flight (a register load would get a compiler wait that drains it).
+//   * K and V of an item are LDS-DMA'd into a [Tp][64] image pair (Tp = 16 NT: 208 rows at T = 197, 53 KB), one of two
+//     slots: the next item streams in while this one computes.  Each wave issues 4 of the item's 4 NT pieces, so HBM
+//     sees a continuous stream instead of the burst at the start of every one-item workgroup.
+//   * Q of the next item is LDS-DMA'd too (2 pieces per wave) and read as MFMA fragments after the next item's
+//     barrier.  Where six images fit in the 160 KiB (T <= 208) Q has a double buffer of its own: the next item's Q and
+//     K / V are issued at the top of the item and there is one barrier per item.  Above that Q goes into the K image
+//     of the current slot once every wave is past its S products (a second barrier), followed by the next K / V into
+//     the other slot.  Every global load is LDS-DMA, so the counted `s_waitcnt vmcnt` at the top of an item retires
+//     this item's K / V / Q pieces and leaves only the previous item's stores in flight (a register load would get a
+//     compiler wait of its own).
 //   * Exact two-pass softmax on 16x16x32 MFMAs: S^T = K Q^T for all keys (NT accumulators of 4: one query per lane
 //     column, keys 4g + i of each 16-key tile on lane group g), the row max and sum over a lane's 4 NT values plus two
 //     permlane swaps, P = exp2(S c2 - max c2) in place, then O^T = V^T P^T with P^T as the B operand straight from the
@@ -1341,16 +1091,11 @@ __global__ __launch_bounds__(NT * 64, 1) void attn_fwd_ring(const bf16_t* __rest
   constexpr int Tp = NT * 16;
   constexpr int IMG = Tp * HD;                        // elements of one [Tp][64] image
   constexpr int SLOT = 2 * IMG;                       // K then V
-// RING_QBUF 1 (default since round 6, r41): two K/V slots + a Q double buffer, one barrier per item — the next item's
-// Q and K / V are issued at the top of the item.  0: three K/V slots (K / V two items ahead) with the next item's Q
-// DMA'd into the current K image after the S products: that Q load sat on the critical path (a timing-only build
-// without the Q pieces ran 17% faster, r40) and the Q buffer form runs 88-92 vs 96-98 us isolated (r41).  Used while
-// the five images fit (T <= 208); above that the three-slot form's two-slot case runs.
-#ifndef RING_QBUF              // A/B builds: 0 = the three-slot form at every T
-#define RING_QBUF 1
-#endif
-  constexpr bool QB = RING_QBUF && 6 * IMG * 2 <= 160 * 1024;
-  constexpr int NS = !QB && 3 * SLOT * 2 <= 160 * 1024 ? 3 : 2;
+  // Two K/V slots, and a Q double buffer while the six images fit (T <= 208).  With the Q load inside the K image it
+  // sits on the critical path (a timing-only build without the Q pieces ran 17% faster); the Q buffer form runs
+  // 88-92 vs 96-98 us isolated at T = 197 (profiles/r42_attn_fwd_ring_qbuf.log).
+  constexpr int NS = 2;
+  constexpr bool QB = (NS * SLOT + 2 * IMG) * 2 <= 160 * 1024;
   __shared__ __attribute__((aligned(16))) bf16_t smem[NS * SLOT + (QB ? 2 * IMG : 0)];
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, ql = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1384,22 +1129,15 @@ __global__ __launch_bounds__(NT * 64, 1) void attn_fwd_ring(const bf16_t* __rest
   // harmless re-reads of the last item into slots nothing reads again — because `s_waitcnt vmcnt(N)` retires all but
   // the N youngest ops: N must never exceed the ops actually issued after the ones it waits for.
   const auto clampi = [&](int64_t x) { return x < items ? x : items - 1; };
-  // prologue: K/V of the first item (slot 0), its Q (the K image of slot NS - 1), K/V of the second (NS = 3: slot 1)
+  // prologue: K/V of the first item (slot 0) and its Q (Q buffer 0, or the K image of slot 1)
   kv_item(it, 0);
   q_item(it, QB ? 0 : NS - 1);
-  if (NS == 3) kv_item(clampi(it + G), 1);
 #pragma unroll 1
   for (int k = 0; it < items; it += G, ++k) {
-    // this item's K / V / Q pieces: the ring's next K / V (4, issued after the 2 Q pieces) and the previous item's 5
-    // stores (4 O + lse: every wave has a valid query row, so none is skipped; 4 more with o32 only make it wait
-    // longer) may stay in flight
-    if (k == 0) {
-      if (NS == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      if (NS == 3) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    }
+    // this item's K / V / Q pieces: the previous item's 5 stores (4 O + lse: every wave has a valid query row, so none
+    // is skipped; 4 more with o32 only make it wait longer) may stay in flight
+    if (k == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's pieces landed
     const int slot = k % NS, pslot = (k + NS - 1) % NS;
     const bf16_t* Ks = smem + slot * SLOT;
@@ -1426,12 +1164,12 @@ __global__ __launch_bounds__(NT * 64, 1) void attn_fwd_ring(const bf16_t* __rest
       a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf0, a, 0, 0, 0);
       s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf1, a, 0, 0, 0);
     }
-    // every wave is past its K and Q reads: the next item's Q into this slot's K image, then the ring's next K / V
-    // into the slot the previous item used (its Q image was read above)
+    // every wave is past its K and Q reads: the next item's Q into this slot's K image, then its K / V into the slot
+    // the previous item used (its Q image was read above)
     if (!QB) {
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       q_item(clampi(it + G), slot);
-      kv_item(clampi(it + (NS - 1) * G), pslot);
+      kv_item(clampi(it + G), pslot);
     }
 
     // keys >= T only in the last tile
@@ -1900,7 +1638,7 @@ extern "C" int vit_attn_fwd(const void* qkv, void* o, float* o32, float* lse, fl
   if (use_mfma(dtype, hd) && probs == nullptr) {
     VIT_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)o) % 16 == 0, "vit_attn_fwd: pointers must be 16-B aligned");
     // (the ring splits item indices with item_bh(): B * H < 2^24; the fused backward's 2 GiB bound implies it there)
-    if (T <= FB_TMAX && !vit::opt(vit::OPT_ATTN_FWD_SPLIT) && vit::opt(vit::OPT_ATTN_FWD_RING) && B * H < (1LL << 24) &&
+    if (T <= FB_TMAX && !vit::opt(vit::OPT_ATTN_FWD_SPLIT) && B * H < (1LL << 24) &&
         3 * H * hd < (1LL << 20)) {                     // (slice_off: 32-bit lane offsets)
       const int64_t items = B * H;
       unsigned grid = (unsigned)std::min<int64_t>(items, vit_cu_count());
@@ -1916,20 +1654,6 @@ extern "C" int vit_attn_fwd(const void* qkv, void* o, float* o32, float* lse, fl
         case 13: RING(13); break; case 14: RING(14); break; case 15: RING(15); break; default: RING(16); break;
       }
 #undef RING
-    } else if (T <= FB_TMAX && B * T * 3 * H * hd * 2 < 0x7fffffffLL && !vit::opt(vit::OPT_ATTN_FWD_SPLIT)) {
-#define FWD(NK) \
-  attn_fwd_fused<NK><<<(unsigned)(B * H), NK * 64, 0, s>>>((const bf16_t*)qkv, (bf16_t*)o, o32, lse, T, H, scale)
-      switch ((int)((T + 31) / 32)) {
-        case 1: FWD(1); break;
-        case 2: FWD(2); break;
-        case 3: FWD(3); break;
-        case 4: FWD(4); break;
-        case 5: FWD(5); break;
-        case 6: FWD(6); break;
-        case 7: FWD(7); break;
-        default: FWD(8); break;
-      }
-#undef FWD
     } else {
       const unsigned grid = (unsigned)(((T + 127) / 128) * B * H);   // 1-D: xcd_block() maps it
       attn_fwd_mfma<<<grid, 256, 0, s>>>((const bf16_t*)qkv, (bf16_t*)o, o32, lse, T, H, scale);

@@ -126,12 +126,30 @@ void colsum_parts_launch(const void* x, int64_t ldx, int dtype, int64_t rows, in
                          float* part, hipStream_t s);
 }  // namespace vit
 
-// Launch options of vit_set_option (vit_hip.h), read by the host-side launchers.
+// Launch options of vit_set_option (vit_hip.h), read by the host-side launchers: X(enumerator, "name", default).
+// The enum below and the name / value tables of vit_misc.hip are all generated from this one list.
+#define VIT_OPTIONS(X)                              \
+  X(OPT_GEMM_IMPL, "gemm_impl", 0)                  \
+  X(OPT_GEMM_TAIL, "gemm_tail", 0)                  \
+  X(OPT_GEMM_TAIL_MIN_KT, "gemm_tail_min_kt", 40)   \
+  X(OPT_GEMM_TAIL_V2, "gemm_tail_v2", 0)            \
+  X(OPT_SPLITK_MIN_KT, "splitk_min_kt", 0)          \
+  X(OPT_SPLITK_ROUNDS, "splitk_rounds", 1)          \
+  X(OPT_GEMM_GROUP_M, "gemm_group_m", 0)            \
+  X(OPT_GEMM_EPI_GENERAL, "gemm_epi_general", 0)    \
+  X(OPT_GEMM_PERSIST, "gemm_persist", 1)            \
+  X(OPT_ATTN_FWD_SPLIT, "attn_fwd_split", 0)        \
+  X(OPT_ATTN_BWD_SPLIT, "attn_bwd_split", 0)        \
+  X(OPT_ATTN_FWD_GRID, "attn_fwd_grid", 0)          \
+  X(OPT_ATTN_BWD_GRID, "attn_bwd_grid", 0)          \
+  X(OPT_LN16, "ln16", 1)                            \
+  X(OPT_LN_AL, "ln_al", 1)
 namespace vit {
 enum Opt : int {
-  OPT_GEMM_IMPL = 0, OPT_GEMM_TAIL, OPT_GEMM_TAIL_MIN_KT, OPT_SPLITK_MIN_KT, OPT_GEMM_GROUP_M, OPT_GEMM_EPI_GENERAL,
-  OPT_GEMM_PERSIST, OPT_ATTN_FWD_SPLIT, OPT_ATTN_BWD_SPLIT, OPT_ATTN_BWD_GRID, OPT_LN16, OPT_LN_AL, OPT_ATTN_FWD_RING,
-  OPT_GEMM_TAIL_V2, OPT_SPLITK_ROUNDS, OPT_ATTN_FWD_GRID, OPT_COUNT
+#define X(ENUM, NAME, DEF) ENUM,
+  VIT_OPTIONS(X)
+#undef X
+  OPT_COUNT
 };
 int64_t opt(Opt o);
 }  // namespace vit

@@ -670,18 +670,12 @@ VIT_DEV void dma_half_g(const char* base, const uint32_t (&off)[2], uint32_t sof
 // LDS ring of the v4 k-loop: V4_SLOTS half-tile images (16 KiB each); stage s (k-tile s/4, half A0/B0/B1/A1) lands in
 // slot s % V4_SLOTS and is issued V4_LEAD phases before the phase that first needs it retired.  A slot is
 // re-staged (stage s + SLOTS, issued in phase s + SLOTS - LEAD) >= 2 phases after stage s's last read (phase <= s),
-// so LEAD <= SLOTS - 2.  Measured (tools/r2g.sh, ViT-B/16 shapes): 10 slots / lead 8 (160 KiB, 6 stages in flight
-// across every barrier) and 10 / 7 are no faster than 8 / 6 (4 stages in flight), so the default stays 8 / 6.
-#ifndef V4_SLOTS
-#define V4_SLOTS 8
-#endif
-#ifndef V4_LEAD
-#define V4_LEAD (V4_SLOTS - 2)
-#endif
+// so LEAD <= SLOTS - 2.  Measured on the ViT-B/16 shapes: 10 slots / lead 8 (160 KiB, 6 stages in flight across every
+// barrier) and 10 / 7 are no faster than 8 / 6 (4 stages in flight), nor are leads 5 and 4
+// (profiles/r55_gemm_lead_ab.log), so it stays 8 / 6.
+constexpr int V4_SLOTS = 8;
+constexpr int V4_LEAD = V4_SLOTS - 2;
 static_assert(V4_LEAD <= V4_SLOTS - 2 && V4_LEAD >= 4 && V4_LEAD <= 8, "v4 ring: 4 <= LEAD <= SLOTS - 2, LEAD <= 8");
-#ifndef V4_DMA_MFMA      // A/B builds: 1 = a phase's LDS-DMA stage issued between its two MFMA half-clusters
-#define V4_DMA_MFMA 0
-#endif
 
 // vmcnt for phase f: the `left` DMA stages younger than s = f+2 that exist may stay in flight (2 instructions each)
 VIT_DEV void wait_stage_retired(int left) {
@@ -708,16 +702,6 @@ VIT_DEV void read_b4(const bf16_t* half, int wc, int lane, bf16x8_t (&bf)[2][2])
   for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
     for (int y = 0; y < 2; ++y) bf[y][kk] = read_frag<BKC>(half, wc * 32 + y * 16, kk, lane);
-}
-
-// Half of a quadrant's MFMAs (k-step kk of the 64-deep k-tile); V4_DMA_MFMA issues the phase's LDS-DMA between the
-// two halves (the MFMA segment), not in the load segment.
-VIT_DEV void mfma_quadrant_half(f32x4 (&acc)[4][2], const bf16x8_t (&af)[4][2], const bf16x8_t (&bf)[2][2], int kk) {
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-      acc[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[y][kk], af[x][kk], acc[x][y], 0, 0, 0);
 }
 
 // (no s_setprio around the cluster: raising the MFMA wave's priority measured 0.5-1.5% slower per GEMM, r53)
@@ -828,10 +812,9 @@ VIT_DEV void v4_epilogue(const EpiParams& e, const GemmArgs& g, const f32x4 (&ac
 // keeps the compiler from moving LDS accesses across it.
 #define V4_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-// Wide row epilogue (bf16 output, fast kinds, rows 8-element aligned — e.vec8): one wave instruction stores two
-// whole 256-column rows, 16 B per lane (lanes 0-31 row r, lanes 32-63 row r + 1).  Per-CU store throughput is set by
-// the number of store instructions (tools/gemm_stamps.py: 8-B-per-lane rows took ~16k cycles per 256^2 tile, half
-// the K = 768 k-loop), so 16-B stores halve it (cdna_hip_programming.md T21).
+// Wide row epilogue (bf16 output, fast kinds, rows 8-element aligned — e.vec8): every lane stores 16-B row pieces.
+// Per-CU store throughput is set by the number of store instructions (a cycle-stamped build: 8-B-per-lane rows took
+// ~16k cycles per 256^2 tile, half the K = 768 k-loop), so 16-B stores halve it (cdna_hip_programming.md T21).
 template <int KIND>
 VIT_DEV uint4 v4_pre_load8(const EpiParams& e, int64_t i, int64_t j) {
   uint4 r = make_uint4(0u, 0u, 0u, 0u);
@@ -936,126 +919,6 @@ VIT_DEV uint32_t v4_epi_row8(const EpiParams& e, int64_t i, int64_t j, bf16_t* c
 #pragma unroll
   for (int r = 0; r < 8; ++r) pos |= (uint32_t)(v[r] > 0.f) << r;
   return pos;
-}
-
-// Accumulator image of the wide epilogue: [128][256] fp32, physical 16-B chunk = c ^ ((c >> 4) & 1) ^ (row & 15).
-// Fragment writes (8 consecutive rows per ds_write_b128 lane group, one chunk) and row-piece reads (lane l of a row
-// reads chunks 2l and 2l+1, one ds_read_b128 each) are both conflict-free, and each lane's two chunks arrive in
-// column order.
-VIT_DEV int v4w_chunk(int row, int c) { return c ^ ((c >> 4) & 1) ^ (row & 15); }
-
-template <int KIND, int ACT, bool MK, bool CS>
-VIT_DEV void v4_epilogue_w(const EpiParams& e, const f32x4 (&acc)[2][2][4][2], float* ep, int tid, int64_t i0,
-                           int64_t j0, int64_t tm) {
-  // ep: a [64][256] fp32 image (64 KiB, ring slots 4-7: the persistent kernel's next-tile stages fill slots 0-3
-  // meanwhile).  Pass k = tile rows [64k, 64k + 64): written by the 4 waves with wr == k & 1 (accumulator half
-  // mh = k >> 1), then read by all 8 waves, 8 rows = 4 row pairs each.
-  const int lane = tid & 63, l = lane & 31, hr = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-  const int64_t j = j0 + 8 * l;
-  const bool jok = j < e.n;                              // n % 8 == 0: a lane's 8 columns are all in or all out
-  float b8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if ((KIND == EPI_BIAS_ACT || KIND == EPI_BDR) && e.bias && jok) {
-    ld4<float>(e.bias + j, b8);
-    ld4<float>(e.bias + j + 4, b8 + 4);
-  }
-  const bool has_pre = v4_has_pre<KIND>(e);
-  // second-operand row pieces (pass k, pair p: row 64k + wave*8 + 2p + hr), one pass ahead of their use
-  uint4 pre[2][4];
-#define V4W_PRE(K)                                                                                  \
-  do {                                                                                              \
-    if (has_pre) {                                                                                  \
-      _Pragma("unroll") for (int p_ = 0; p_ < 4; ++p_) {                                            \
-        if (KIND != EPI_AUXM || (p_ & 1) == 0)                                                      \
-          pre[(K) & 1][p_] = v4_pre_load8<KIND>(e, i0 + 64 * (K) + wave * 8 + 2 * p_ + hr, j);       \
-        else                                                                                        \
-          pre[(K) & 1][p_] = pre[(K) & 1][p_ - 1];    /* rows 2p-2+hr, 2p+hr: one mask4 row group */ \
-      }                                                                                             \
-    }                                                                                               \
-  } while (0)
-  V4W_PRE(0);
-  float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  uint32_t mlo = 0u, mhi = 0u;                          // mask4 dwords of column groups 2l, 2l+1 being assembled
-  V4_LDS_BARRIER();                                     // every wave's k-loop reads of slots 4-7 are done
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (k < 3) V4W_PRE(k + 1);
-    if (wr == (k & 1)) {
-#pragma unroll
-      for (int nh = 0; nh < 2; ++nh)
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-#pragma unroll
-          for (int y = 0; y < 2; ++y) {
-            const int row = x * 16 + (lane & 15);
-            const int chunk = (nh * 128 + wc * 32 + y * 16) / 4 + (lane >> 4);
-            *reinterpret_cast<f32x4*>(ep + row * 256 + (v4w_chunk(row, chunk) << 2)) = acc[k >> 1][nh][x][y];
-          }
-    }
-    V4_LDS_BARRIER();
-    f32x4 rv[4][2];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int row = wave * 8 + 2 * p + hr;
-      rv[p][0] = *reinterpret_cast<const f32x4*>(ep + row * 256 + (v4w_chunk(row, 2 * l) << 2));
-      rv[p][1] = *reinterpret_cast<const f32x4*>(ep + row * 256 + (v4w_chunk(row, 2 * l + 1) << 2));
-    }
-    // uniform row base of this wave's 8 rows; per lane a 32-bit element offset
-    const int64_t rbase = i0 + 64 * k + wave * 8;
-    const int rows_left = (int)min((int64_t)8, max((int64_t)0, e.m - rbase));
-    bf16_t* cbase = (bf16_t*)e.c + rbase * e.ldc + j0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      float v[8] = {rv[p][0][0], rv[p][0][1], rv[p][0][2], rv[p][0][3],
-                    rv[p][1][0], rv[p][1][1], rv[p][1][2], rv[p][1][3]};
-      const int rr = 2 * p + hr;
-      const int64_t i = rbase + rr;
-      const int sh = 8 * (rr & 3);
-      uint32_t bits = 0u;
-      if (jok && rr < rows_left) {
-        bf16_t* cp = cbase + (uint32_t)(rr * (int)e.ldc + 8 * l);
-        bits = v4_epi_row8<KIND, ACT, MK, CS>(e, i, j, cp, b8, v, has_pre ? pre[k & 1][p] : make_uint4(0u, 0u, 0u, 0u),
-                                             sh);
-        if (CS) {
-#pragma unroll
-          for (int r = 0; r < 8; ++r) cs[r] += v[r];
-        }
-      }
-      if (MK) {
-        mlo |= (bits & 0xfu) << sh;
-        mhi |= ((bits >> 4) & 0xfu) << sh;
-        if (p & 1) {
-          // rows 4q..4q+3 done: lane l (hr 0) holds bytes 0, 2 and lane l+32 bytes 1, 3 of both dwords; lane l
-          // stores column group 2l, lane l+32 column group 2l+1
-          const uint32_t recv = (uint32_t)__shfl_xor((int)(hr ? mlo : mhi), 32, 64);
-          if (2 * (p - 1) < rows_left && jok)
-            *reinterpret_cast<uint32_t*>(e.mask_out + mask4_byte(rbase + 2 * (p - 1), j + 4 * hr, e.n)) =
-                (hr ? mhi : mlo) | recv;
-          mlo = mhi = 0u;
-        }
-      }
-    }
-    if (k < 3) V4_LDS_BARRIER();                        // the next pass overwrites the image
-  }
-#undef V4W_PRE
-  if (CS) {
-    // even + odd rows of the wave, then the 8 wave sums in wave order through LDS: one row of csum per tile
-#pragma unroll
-    for (int r = 0; r < 8; ++r) cs[r] += __shfl_xor(cs[r], 32, 64);
-    V4_LDS_BARRIER();
-    if (hr == 0) {
-      *reinterpret_cast<f32x4*>(ep + wave * 256 + 8 * l) = f32x4{cs[0], cs[1], cs[2], cs[3]};
-      *reinterpret_cast<f32x4*>(ep + wave * 256 + 8 * l + 4) = f32x4{cs[4], cs[5], cs[6], cs[7]};
-    }
-    V4_LDS_BARRIER();
-    if (tid < 256 && j0 + tid < e.n) {
-      float sum = 0.f;
-#pragma unroll
-      for (int w8 = 0; w8 < 8; ++w8) sum += ep[w8 * 256 + tid];
-      e.csum[tm * e.n + j0 + tid] = sum;
-    }
-  }
 }
 
 // Direct wide epilogue (the persistent kernel's; no LDS image): in the 16x16 MFMA fragment a lane holds 4 consecutive
@@ -1178,17 +1041,6 @@ VIT_DEV void v4_epilogue_dd(const EpiParams& e, f32x4 (&acc)[2][2][4][2], float*
   else v4_epilogue_d<KIND, ACT, false, false>(e, acc, cs_lds, tid, i0, j0, tm);
 }
 
-// mask / column-sum switches of the wide epilogue as template arguments (no dead per-row work when off)
-template <int KIND, int ACT>
-VIT_DEV void v4_epilogue_wd(const EpiParams& e, const f32x4 (&acc)[2][2][4][2], float* ep, int tid, int64_t i0,
-                            int64_t j0, int64_t tm) {
-  const bool mk = e.mask_out != nullptr, cs = e.csum != nullptr;
-  if (mk && cs) v4_epilogue_w<KIND, ACT, true, true>(e, acc, ep, tid, i0, j0, tm);
-  else if (mk) v4_epilogue_w<KIND, ACT, true, false>(e, acc, ep, tid, i0, j0, tm);
-  else if (cs) v4_epilogue_w<KIND, ACT, false, true>(e, acc, ep, tid, i0, j0, tm);
-  else v4_epilogue_w<KIND, ACT, false, false>(e, acc, ep, tid, i0, j0, tm);
-}
-
 // Work item -> (tile row, tile column, K-slice).  Items are split-major (all tiles of K-slice 0, then slice 1, ...);
 // with group_m > 1 the tiles go in groups of group_m tile rows, column-major inside a group (L2 locality: the ~32
 // tiles an XCD runs at once span group_m A panels x 32/group_m B panels).
@@ -1223,10 +1075,10 @@ VIT_DEV void v4_offsets(const GemmArgs& g, int64_t i0, int64_t j0, int64_t k0, i
 
 // Persistent form (the wide-epilogue kinds: bf16 output, fast epilogue; the host launches one workgroup per CU): a
 // workgroup loops over its items, and as soon as a tile's k-loop is done it issues the NEXT tile's first 4 stages
-// (LDS ring slots 0-3, whose last reads are behind the k-loop's final barrier) before running the epilogue on a
-// 64 KiB image in slots 4-7 — the next tile's pipeline fill overlaps the epilogue instead of following it
-// (tools/gemm_stamps.py: the fill was ~5.5k cycles of a ~50k-cycle K = 768 tile).  Other kinds (split-K slabs, fp32
-// or general epilogues) run one item per workgroup with the 128 KiB image, as before.
+// (LDS ring slots 0-3, whose last reads are behind the k-loop's final barrier) before running the direct epilogue,
+// which needs no LDS image — the next tile's pipeline fill overlaps the epilogue instead of following it (a
+// cycle-stamped build: the fill was ~5.5k cycles of a ~50k-cycle K = 768 tile).  Other kinds (split-K slabs, fp32 or
+// general epilogues) run one item per workgroup with the 128 KiB image.
 template <bool AKC, bool BKC, class TO, int KIND>
 __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, int64_t a_bytes, int64_t b_bytes) {
   // the ring, then 2 KiB for the direct epilogue's column-sum combine
@@ -1259,7 +1111,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
   v4_offsets<AKC, BKC>(g, i0, j0, sidx * g.kt_per_split * BK, wave, remat(lane), oa0, oa1, ob0, ob1);
   const char* pa_ = (const char*)g.a;
   const char* pb_ = (const char*)g.b;
-#define V4_DMA(R, P, OFF, SOFF, DST) dma_half_g(P, OFF, SOFF, DST, wave)
+#define V4_DMA(P, OFF, SOFF, DST) dma_half_g(P, OFF, SOFF, DST, wave)
 
   // stage s -> (k-tile s>>2, half order A0, B0, B1, A1) in LDS slot s % V4_SLOTS
 #define V4_SLOT(S) (smem4 + ((S) % V4_SLOTS) * HALF)
@@ -1268,10 +1120,10 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
     const int s_ = (S), u_ = s_ >> 2;                                                            \
     bf16_t* slot_ = V4_SLOT(s_);                                                                 \
     switch (s_ & 3) {                                                                            \
-      case 0: V4_DMA(ra, pa_, oa0, (uint32_t)u_ * sa, slot_); break;                             \
-      case 1: V4_DMA(rb, pb_, ob0, (uint32_t)u_ * sb, slot_); break;                             \
-      case 2: V4_DMA(rb, pb_, ob1, (uint32_t)u_ * sb, slot_); break;                             \
-      default: V4_DMA(ra, pa_, oa1, (uint32_t)u_ * sa, slot_); break;                            \
+      case 0: V4_DMA(pa_, oa0, (uint32_t)u_ * sa, slot_); break;                                 \
+      case 1: V4_DMA(pb_, ob0, (uint32_t)u_ * sb, slot_); break;                                 \
+      case 2: V4_DMA(pb_, ob1, (uint32_t)u_ * sb, slot_); break;                                 \
+      default: V4_DMA(pa_, oa1, (uint32_t)u_ * sa, slot_); break;                                \
     }                                                                                            \
   } while (0)
 
@@ -1296,31 +1148,6 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
 
     // One phase f = 4t + r.  STEADY: the k-tiles before the last two, where every phase issues its DMA stage and the
     // retiring wait is the constant vmcnt(2 * (LEAD - 2)) — no per-phase branches (the tail's counts are computed).
-#if V4_DMA_MFMA
-    // the stage goes out in the MFMA segment (below), after this wait: one stage fewer is in flight here
-#define V4_PHASE_DMA(F, STEADY)                                                                  \
-  do {                                                                                           \
-    if (STEADY) wait_stage_retired(V4_LEAD - 3);                                                 \
-    else wait_stage_retired(min(V4_LEAD - 3, nstage - 1 - ((F) + 2)));                           \
-  } while (0)
-#define V4_MFMA_DMA(ACC, BF, F, STEADY)                                                          \
-  do {                                                                                           \
-    __builtin_amdgcn_s_setprio(1);                                                               \
-    mfma_quadrant_half(ACC, af, BF, 0);                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    if (STEADY || (F) + V4_LEAD < nstage) V4_STAGE((F) + V4_LEAD);                               \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    mfma_quadrant_half(ACC, af, BF, 1);                                                          \
-    __builtin_amdgcn_s_setprio(0);                                                               \
-  } while (0)
-#define V4_PHASE_MFMA(R, F, STEADY)                                                              \
-  do {                                                                                           \
-    if ((R) == 0) V4_MFMA_DMA(acc[0][0], b0f, F, STEADY);                                        \
-    else if ((R) == 1) V4_MFMA_DMA(acc[0][1], b1f, F, STEADY);                                   \
-    else if ((R) == 2) V4_MFMA_DMA(acc[1][1], b1f, F, STEADY);                                   \
-    else V4_MFMA_DMA(acc[1][0], b0f, F, STEADY);                                                 \
-  } while (0)
-#else
 #define V4_PHASE_DMA(F, STEADY)                                                                  \
   do {                                                                                           \
     if (STEADY) {                                                                                \
@@ -1338,7 +1165,6 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
     else if ((R) == 2) mfma_quadrant(acc[1][1], af, b1f);                                        \
     else mfma_quadrant(acc[1][0], af, b0f);                                                      \
   } while (0)
-#endif
 #define V4_PHASE(T, R, STEADY)                                                                   \
   do {                                                                                           \
     const int f_ = 4 * (T) + (R);                                                                \
@@ -1376,9 +1202,6 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
 #undef V4_PHASE
 #undef V4_PHASE_MFMA
 #undef V4_PHASE_DMA
-#ifdef V4_MFMA_DMA
-#undef V4_MFMA_DMA
-#endif
     if (wr == 0) __builtin_amdgcn_s_barrier();            // balance group 1's extra barrier
 
     // next item: its first stages go out now (slots 0-3), ahead of this tile's epilogue
@@ -1547,8 +1370,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 bool aligned(const void* p, int a) { return p == nullptr || (((uintptr_t)p) % a) == 0; }
 
-// bf16 kernels: 1 = register-staged 128x128, 2 = LDS-DMA 128x128, 4 = LDS-DMA 256x256 ping-pong with LDS-staged
-// epilogue (3 = 4: the former 256-row experiment was removed).
+// bf16 kernels: 1 = register-staged 128x128, 2 = LDS-DMA 128x128, 4 = LDS-DMA 256x256 ping-pong.
 // Option "gemm_impl" forces a kernel (A/B runs and the per-variant tests); 0 = automatic: v4 when both output dims
 // span a 256 tile, else v2.
 int gemm_impl_env() {
@@ -1718,7 +1540,7 @@ static int gemm_run(const vit_gemm_desc* d, int64_t row0, void* stream, int forc
     const int impl = force_impl ? force_impl : gemm_impl(d->m, d->n);
     const bool dma_ok = d->k % BK == 0 && a_bytes < 0x7fffffffLL && b_bytes < 0x7fffffffLL;
     const bool v2 = impl == 2 && dma_ok;
-    const bool v4 = (impl == 4 || impl == 3) && dma_ok;
+    const bool v4 = impl == 4 && dma_ok;
     GemmArgs g4 = g;
     g4.tiles_n = (d->n + 255) / 256;
     g4.tiles_m = (d->m + 255) / 256;

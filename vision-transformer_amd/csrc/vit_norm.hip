@@ -7,9 +7,7 @@
 namespace {
 
 constexpr int LN_BWD_PARTS_MAX = 2048;
-#ifndef LN_BWD_RPB
-#define LN_BWD_RPB 32       // rows per backward block (its dgamma / dbeta partial covers them); 16 and 64 measured slower
-#endif
+constexpr int LN_BWD_RPB = 32;  // rows per backward block (its dgamma / dbeta partial covers them); 16 and 64 measured slower
 
 template <class T, int NV>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, int64_t ldx,
