@@ -27,7 +27,7 @@ from oracle import vit_oracle as O
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
-    from VisionTransformer import _lib, _ops, config, vit
+    from VisionTransformer import _engine, _lib, _ops, config, vit
     from VisionTransformer.optim import FusedAdamW, cross_entropy
 
 DEV = "cuda"
@@ -662,7 +662,7 @@ def test_vit_base_depth12_teacher_forced_blocks_bf16():
     eng.ensure_ready(xd.device)
     req = {k: True for k in eng.owners}
     rnd = O._RoundBF16.apply
-    names = ["qkv_w", "proj_w", "proj_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b"]
+    names = _engine.BLOCK_REGIONS
     bad, report = [], []
     for l in range(L):
         x_in = ins[l].detach().bfloat16()
@@ -671,7 +671,7 @@ def test_vit_base_depth12_teacher_forced_blocks_bf16():
         x_out, saved = eng.block_forward(l, x_in.view(M, D).contiguous(), B, True, seed, True)
         eng.G.zero_()
         dxo = dy.view(M, D).contiguous()
-        g1 = _ops.mask4_apply(dxo, torch.empty_like(dxo), saved[15], 1.0)
+        g1 = _ops.mask4_apply(dxo, torch.empty_like(dxo), saved.fm, 1.0)
         dx_in, _ = eng.block_backward(l, saved, dxo, g1, False, 0.0, req, None, True, B)
         torch.cuda.synchronize()
         ours = {n: eng.gw[f"{l}.{n}"].double().clone() for n in names}

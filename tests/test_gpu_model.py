@@ -450,13 +450,7 @@ def test_side_stream_weight_gradients_bitwise_equal():
     assert torch.equal(gs[0], gs[1])
 
 
-@pytest.mark.parametrize("dtype,img,train", [(torch.bfloat16, 224, True), (torch.bfloat16, 224, False),
-                                             (torch.float32, 64, True), (torch.bfloat16, 64, True)])
-def test_two_stream_forward_bitwise_equal(dtype, img, train):
-    """The forward's encoder blocks as two half-batch chains on two streams (engine.fwd_streams = 2, the default for
-    batches divisible by 8) equal one chain bit for bit: logits, loss, every gradient (the backward reads the same
-    saved tensors), dropout bits included — the half-batch GEMMs draw the whole batch's dropout indices (vit_gemm_desc
-    dropout_row0).  ViT-B width, 2 blocks (the second pruned, with the query-0 attention), B = 8."""
+def _two_stream_vs_one(dtype, img, train, prune_last=True, row0_attention=True):
     ocfg = O.make_config("micro", img=img, batch=8, blocks=2)
     ocfg.embedding_size, ocfg.num_heads = 768, 12
     st = O.init_state(ocfg, seed=8)
@@ -467,6 +461,7 @@ def test_two_stream_forward_bitwise_equal(dtype, img, train):
         m.load_state_dict(st)
         m.train(train)
         m.hip_engine.fwd_streams = streams
+        m.hip_engine.prune_last, m.hip_engine.row0_attention = prune_last, row0_attention
         torch.manual_seed(5)
         logits = m(x.to(DEV))
         loss = cross_entropy(logits, y.to(DEV))
@@ -476,6 +471,24 @@ def test_two_stream_forward_bitwise_equal(dtype, img, train):
     assert torch.equal(out[0][0], out[1][0])
     assert torch.equal(out[0][1], out[1][1])
     assert torch.equal(out[0][2], out[1][2])
+
+
+@pytest.mark.parametrize("dtype,img,train", [(torch.bfloat16, 224, True), (torch.bfloat16, 224, False),
+                                             (torch.float32, 64, True), (torch.bfloat16, 64, True)])
+def test_two_stream_forward_bitwise_equal(dtype, img, train):
+    """The forward's encoder blocks as two half-batch chains on two streams (engine.fwd_streams = 2, the default for
+    batches divisible by 8) equal one chain bit for bit: logits, loss, every gradient (the backward reads the same
+    saved tensors), dropout bits included — the half-batch GEMMs draw the whole batch's dropout indices (vit_gemm_desc
+    dropout_row0).  ViT-B width, 2 blocks (the second pruned, with the query-0 attention), B = 8."""
+    _two_stream_vs_one(dtype, img, train)
+
+
+@pytest.mark.parametrize("prune_last,row0_attention", [(True, False), (False, True)])
+def test_two_stream_forward_bitwise_equal_last_block_modes(prune_last, row0_attention):
+    """... and so with the other forms of the last block: pruned with the full attention (after the chains join, with
+    no per-chain ln1 / K-V pass), and not pruned at all (every block split, none after the join).  The smallest case
+    above: bf16, 64^2, training, B = 8 (the smallest batch the split takes), 2 blocks (one split, one last)."""
+    _two_stream_vs_one(torch.bfloat16, 64, True, prune_last, row0_attention)
 
 
 def test_two_stream_forward_no_grad_bitwise_equal():
@@ -644,7 +657,7 @@ def _engine_relu_masks(m, x, L, B, T, D, own):
     _, tape = m.hip_engine.forward(x, False, True)
     out = {}
     for l in range(L):
-        hm = tape.blocks[l][13]
+        hm = tape.blocks[l].hm
         R = B if (tape.pruned and l == L - 1) else B * T
         ones = torch.ones(R, 4 * D, device=DEV)
         bits = _ops.mask4_apply(ones, torch.empty_like(ones), hm, 1.0) > 0

@@ -91,7 +91,7 @@ def _keep_bits(m, x, seed):
     """proj-dropout keep bits (VIT_MASK4 bytes) of block 0 in one training forward drawn under CPU seed `seed`."""
     torch.manual_seed(seed)
     _, tape = m.hip_engine.forward(x, True, save=True)
-    return tape.blocks[0][14].cpu().numpy()
+    return tape.blocks[0].pm.cpu().numpy()
 
 
 def _ddp_train_worker(rank, world, port, q):

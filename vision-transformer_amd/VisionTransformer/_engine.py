@@ -18,9 +18,10 @@ Layouts (device):
 """
 from __future__ import annotations
 
+import contextlib
 import math
-import os
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -97,9 +98,54 @@ def head_split_for(m, n, k):
 
 
 class Tape:
-    """Activations saved by a training forward."""
+    """Activations saved by a training forward (`blocks`: one BlockActs per encoder block)."""
     __slots__ = ("B", "cols", "blocks", "z", "u", "gz", "zn", "mh", "rh", "seed", "training", "x_shape", "x_dtype",
                  "x_grad", "pruned", "row0")
+
+
+# per-block gradient regions, in their order in the flat gradient buffer (qkv_w: the fused [3D, D] matrix of every head)
+BLOCK_REGIONS = ("qkv_w", "proj_w", "proj_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b")
+
+
+class BlockActs(NamedTuple):
+    """The tensors one encoder block's forward writes (Engine._block_bufs allocates them, block_forward fills them)
+    and, on the tape, what block_backward reads.  M = B*T rows; R = M, or B in the pruned last block (token-0 rows)."""
+    x_in: torch.Tensor      # [M, D] block input
+    a1: torch.Tensor        # [M, D] ln1(x_in), with mean / rstd m1, r1 [M] (fp32)
+    m1: torch.Tensor
+    r1: torch.Tensor
+    qkv: torch.Tensor       # [M, 3D]
+    o: torch.Tensor         # [M, D] attention output
+    o32: Optional[torch.Tensor]   # [M, D] fp32 O, where the attention backward takes it (attn_bwd_uses_o32)
+    lse: torch.Tensor       # [B, H, T] fp32
+    x_mid: torch.Tensor     # [R, D] x_in + drop(proj(o))
+    a2: torch.Tensor        # [R, D] ln2(x_mid), with m2, r2 [R]
+    m2: torch.Tensor
+    r2: torch.Tensor
+    h: torch.Tensor         # [R, 4D] relu(fc1(a2))
+    hm: Optional[torch.Tensor]    # mask4 of h > 0 (saving forwards)
+    pm: Optional[torch.Tensor]    # mask4 keep bits of the proj dropout (saving training forwards)
+    fm: Optional[torch.Tensor]    # ... and of the fc2 dropout
+
+    def images(self, b0, B, T):
+        """Images b0 .. b0+B-1 of this whole-batch (unpruned) record, as views: T rows per image, lse by image, the
+        mask4 tensors by 4-row group (b0*T and B*T multiples of 4)."""
+        r0, R = b0 * T, B * T
+        D = self.x_mid.shape[1]
+
+        def rows(t):
+            return None if t is None else t[r0:r0 + R]
+
+        def bits(mask, n):          # the byte range of rows r0 .. r0+R-1 in the VIT_MASK4 of an [.., n] tensor
+            if mask is None:
+                return None
+            off = (r0 // 4) * ((n + 3) // 4) * 4
+            return mask[off:off + _ops.mask4_bytes(R, n)]
+
+        s = self
+        return BlockActs(x_in=rows(s.x_in), a1=rows(s.a1), m1=rows(s.m1), r1=rows(s.r1), qkv=rows(s.qkv), o=rows(s.o),
+                         o32=rows(s.o32), lse=s.lse[b0:b0 + B], x_mid=rows(s.x_mid), a2=rows(s.a2), m2=rows(s.m2),
+                         r2=rows(s.r2), h=rows(s.h), hm=bits(s.hm, 4 * D), pm=bits(s.pm, D), fm=bits(s.fm, D))
 
 
 class Engine:
@@ -128,7 +174,7 @@ class Engine:
         self.time_comm = False
         self._comm_events = None
         self._works = []
-        self._ws = None
+        self._ws = [None, None]      # grow-only fp32 scratch: main stream, weight-gradient side stream (_workspace)
         self._tok = None
         self._ptr_sig = None
         self._ver_sig = None
@@ -146,13 +192,11 @@ class Engine:
         # the forward's encoder blocks as two half-batch chains on two HIP streams (_forward_blocks_split): each fills
         # the other's idle CUs (partial last rounds of tiles, kernel drains); outputs bitwise those of one chain
         self.fwd_streams = 2
-        self._split_fwd = False
         self._fwd_pair = None
         # backward kernels share the CUs with RCCL collectives (set by enable_data_parallel on the nccl backend;
         # an attribute, so A/B runs can force either launch mode)
         self.shared_cus = False
         self._wstream = None
-        self._wws = None
         # the last block's post-attention part on the B token-0 rows only (see forward); False: every row (tests)
         self.prune_last = True
         # ... and its attention on query 0 alone (vit_attn_fwd_row0 / vit_attn_bwd_row0); False: the full attention
@@ -167,6 +211,10 @@ class Engine:
         # an attribute for A/B runs
         self.defer_grad_attach = True
         self._pending_views = None
+        # left by backward() for run_param_hooks(): the gradients from before an accumulating backward with
+        # `register_hook` hooks, and the frozen per-head views inside a QKV region that was rewritten
+        self._acc_old = None
+        self._frozen_keep = None
 
     # ------------------------------------------------------------------------------------------------------------
     # layout
@@ -194,97 +242,64 @@ class Engine:
         return p
 
     def _build(self, model, device):
-        D, H, hd, L = self.D, self.H, self.hd, self.L
+        D, hd, L = self.D, self.hd, self.L
         params = self._collect(model)
         for n, t in params.items():
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError(f"parameter {n} must be contiguous float32 master weights (got {t.dtype})")
             if t.device != device:
                 raise RuntimeError(f"parameter {n} is on {t.device}, expected {device}; call model.to(device)")
+
+        def shape(name):       # of a region: its parameter's, but for the fused QKV and the conv-as-GEMM matrices
+            if name.endswith(".qkv_w"):
+                return (3 * D, D)
+            return (D, self.CPP) if name == "conv_w" else tuple(params[name].shape)
+
         # ---- gradient layout: head | blocks L-1..0 | embedding
         g = _Region()
-        goff = {}
-        head_start = g.size
-        for n in ("h0_w", "h0_b", "hln_w", "hln_b", "h3_w", "h3_b"):
-            goff[n] = g.add(n, params[n].numel())
-        self.head_range = (head_start, g.size)
-        self.block_range = {}
-        for l in reversed(range(L)):
+
+        def grads(names):
             start = g.size
-            goff[f"{l}.qkv_w"] = g.add(f"{l}.qkv_w", 3 * D * D)
-            for n in ("proj_w", "proj_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b"):
-                goff[f"{l}.{n}"] = g.add(f"{l}.{n}", params[f"{l}.{n}"].numel())
-            self.block_range[l] = (start, g.size)
-        start = g.size
-        for n in ("conv_w", "conv_b", "cls", "pos"):
-            goff[n] = g.add(n, params[n].numel())
-        self.embed_range = (start, g.size)
+            for n in names:
+                g.add(n, math.prod(shape(n)))
+            return start, g.size
+
+        self.head_range = grads(("h0_w", "h0_b", "hln_w", "hln_b", "h3_w", "h3_b"))
+        self.block_range = {l: grads([f"{l}.{n}" for n in BLOCK_REGIONS]) for l in reversed(range(L))}
+        self.embed_range = grads(("conv_w", "conv_b", "cls", "pos"))
         self.G = torch.zeros(g.size, dtype=torch.float32, device=device)
-        # ---- compute shadow layout
+        # ---- compute shadow layout: the blocks' matrices, then the patch embedding's
         s = _Region()
-        soff = {}
-        for l in range(L):
-            soff[f"{l}.qkv_w"] = s.add(f"{l}.qkv_w", 3 * D * D)
-            for n in ("proj_w", "fc1_w", "fc2_w"):
-                soff[f"{l}.{n}"] = s.add(f"{l}.{n}", params[f"{l}.{n}"].numel())
-        soff["conv_w"] = s.add("conv_w", params["conv_w"].numel())
+        for name in [f"{l}.{n}" for l in range(L) for n in BLOCK_REGIONS] + ["conv_w"]:
+            if len(shape(name)) == 2:
+                s.add(name, math.prod(shape(name)))
         self.W = torch.empty(s.size, dtype=self.dtype, device=device)
-
-        def gview(name, shape):
-            o = goff[name]
-            n = math.prod(shape)
-            return self.G[o:o + n].view(shape)
-
-        def wview(name, shape):
-            o = soff[name]
-            n = math.prod(shape)
-            return self.W[o:o + n].view(shape)
-
         # fused compute/grad views
-        self.gw, self.ww = {}, {}
-        for l in range(L):
-            self.gw[f"{l}.qkv_w"] = gview(f"{l}.qkv_w", (3 * D, D))
-            self.ww[f"{l}.qkv_w"] = wview(f"{l}.qkv_w", (3 * D, D))
-            for n in ("proj_w", "fc1_w", "fc2_w"):
-                shp = tuple(params[f"{l}.{n}"].shape)
-                self.gw[f"{l}.{n}"] = gview(f"{l}.{n}", shp)
-                self.ww[f"{l}.{n}"] = wview(f"{l}.{n}", shp)
-            for n in ("proj_b", "fc1_b", "fc2_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b"):
-                self.gw[f"{l}.{n}"] = gview(f"{l}.{n}", tuple(params[f"{l}.{n}"].shape))
-        for n in ("h0_w", "h0_b", "hln_w", "hln_b", "h3_w", "h3_b", "conv_b", "cls", "pos"):
-            self.gw[n] = gview(n, tuple(params[n].shape))
-        self.gw["conv_w"] = gview("conv_w", (D, self.CPP))
-        self.ww["conv_w"] = wview("conv_w", (D, self.CPP))
+        self.gw = {n: self.G[o:o + k].view(shape(n)) for n, o, k in g.items}
+        self.ww = {n: self.W[o:o + k].view(shape(n)) for n, o, k in s.items}
 
         # per-parameter grad view + shadow view (the optimizer refreshes the shadow in its kernel)
         self.grad_views = []
         self.grad_region = []           # gradient region (key of self.gw / self.owners) of each grad view
+        self.owners = {}                # which parameters feed each region (a fused QKV region: 3H per-head ones)
         self.pack_entries = []
         for name, p in params.items():
-            l, _, short = name.partition(".") if "." in name else ("", "", name)
-            if short and short[0] in "qkv" and short[1:].isdigit():
-                h = int(short[1:])
-                row0 = {"q": 0, "k": D, "v": 2 * D}[short[0]] + h * hd
-                gv = self.gw[f"{l}.qkv_w"][row0:row0 + hd]
-                sv = self.ww[f"{l}.qkv_w"][row0:row0 + hd]
-                self.grad_region.append(f"{l}.qkv_w")
-            else:
-                key = name
-                gv = self.gw[key].view(p.shape)
-                sv = self.ww[key].view(p.shape) if key in self.ww else None
-                self.grad_region.append(key)
+            key, rows = name, slice(None)
+            l, _, short = name.partition(".")
+            if short[:1] in ("q", "k", "v") and short[1:].isdigit():    # head `h`'s hd rows of the fused QKV region
+                key = f"{l}.qkv_w"
+                r0 = "qkv".index(short[0]) * D + int(short[1:]) * hd
+                rows = slice(r0, r0 + hd)
+            gv = self.gw[key][rows].view(p.shape)
+            sv = self.ww[key][rows].view(p.shape) if key in self.ww else None
             self.grad_views.append((p, gv))
+            self.grad_region.append(key)
+            self.owners.setdefault(key, []).append(p)
             SHADOWS[p] = sv
             if sv is not None:
                 self.pack_entries.append((p, sv))
         self.params = params
         self.param_list = list(params.values())
-        # which parameters feed each gradient region (a fused QKV region serves 3H per-head parameters)
-        self.owners = {}
-        for name, p in params.items():
-            l, _, short = name.partition(".") if "." in name else ("", "", name)
-            key = f"{l}.qkv_w" if (short and short[0] in "qkv" and short[1:].isdigit()) else name
-            self.owners.setdefault(key, []).append(p)
         self.device = device
         self._pack_table = None
         self._ptr_sig = self._pointer_signature()
@@ -333,10 +348,16 @@ class Engine:
             buf = self._tok[key] = torch.zeros(M, D, dtype=dt, device=dev)
         return buf
 
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() * 4 < nbytes:
-            self._ws = torch.empty(max(nbytes // 4 + 1, 1 << 20), dtype=torch.float32, device=self.device)
-        return self._ws
+    def _workspace(self, nbytes, side=False):
+        """Grow-only fp32 scratch of >= nbytes: the main stream's, or (`side`) the weight-gradient stream's."""
+        ws = self._ws[side]
+        if ws is None or ws.numel() * 4 < nbytes:
+            ws = self._ws[side] = torch.empty(max(nbytes // 4 + 1, 1 << 20), dtype=torch.float32, device=self.device)
+        return ws
+
+    def _split_ws(self, split, m, n, side=False):
+        """The split-K slabs of an [m, n] GEMM: `split` fp32 copies of the output (None without a split)."""
+        return self._workspace(split * m * n * 4, side) if split > 1 else None
 
     def _side_stream(self):
         """HIP stream for the weight-gradient GEMMs of the backward (None: run them in order on the current stream).
@@ -364,65 +385,28 @@ class Engine:
         """out[m][n] (+)= alpha sum_r dy[r][i] x[r][j]: weight gradient, reduction over B*T rows, split-K.  With `side`
         it runs on that stream after everything already enqueued on the current one."""
         split = split_k_for(m, n, k, dy.dtype)
-        need = split * m * n * 4 if split > 1 else 0
-        if side is None:
-            ws = self._workspace(need) if split > 1 else None
-            if fam:
-                self._mark(fam, 0, 2.0 * m * n * k, (m + n) * k * dy.element_size() + m * n * 4 * (1 + (beta != 0)))
-            _ops.gemm(dy, x, out, m, n, k, ld_dy, ld_x, out.stride(0), a_kcontig=False, b_kcontig=False, beta=beta,
-                      alpha=alpha, split_k=split, workspace=ws)
-            if fam:
-                self._mark(fam, 1)
-            return
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        ws = None
-        if need:
-            if self._wws is None or self._wws.numel() * 4 < need:
-                self._wws = torch.empty(max(need // 4 + 1, 1 << 20), dtype=torch.float32, device=self.device)
-            ws = self._wws
+        ws = self._split_ws(split, m, n, side is not None)
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream(self.device))
+        elif fam:
+            self._mark(fam, 0, 2.0 * m * n * k, (m + n) * k * dy.element_size() + m * n * 4 * (1 + (beta != 0)))
         _ops.gemm(dy, x, out, m, n, k, ld_dy, ld_x, out.stride(0), a_kcontig=False, b_kcontig=False, beta=beta,
                   alpha=alpha, split_k=split, workspace=ws, stream=side)
-        for t in (dy, x) if ws is None else (dy, x, ws):
-            t.record_stream(side)          # the caching allocator must not hand these out before `side` is done
+        if side is not None:
+            for t in (dy, x) if ws is None else (dy, x, ws):
+                t.record_stream(side)      # the caching allocator must not hand these out before `side` is done
+        elif fam:
+            self._mark(fam, 1)
 
     def _gemm_rows(self, pr, a, b, c, m, n, k, lda, ldb, ldc, **kw):
         """A token-row GEMM; `pr` (the pruned last block, m = B rows): split-K over the otherwise idle CUs — a few
-        256x256 tiles would each run one long k-loop on one CU.  (Two-stream forward: each call gets its own slabs,
-        allocated on its stream, instead of the shared workspace.)"""
+        256x256 tiles would each run one long k-loop on one CU."""
         split = split_k_for(m, n, k, a.dtype) if pr else 1
-        if split > 1:
-            kw.update(split_k=split, workspace=None if self._split_fwd else self._workspace(split * m * n * 4))
-        return _ops.gemm(a, b, c, m, n, k, lda, ldb, ldc, **kw)
-
-    @staticmethod
-    def _rows_of(bufs, b0, B, T):
-        """rows(name, token0): this call's slice (images b0 .. b0+B-1) of the whole-batch buffer bufs[name] — T rows
-        per image, or one (token0: the pruned block's token-0 rows); lse by image.  None without bufs."""
-        def rows(name, token0=False):
-            if bufs is None:
-                return None
-            t = bufs[name]
-            per = 1 if (token0 or name == "lse") else T
-            return t[b0 * per:(b0 + B) * per]
-        return rows
-
-    @staticmethod
-    def _mask4_out(bufs, name, r0, R, n, dev):
-        """A VIT_MASK4 buffer for rows r0 .. r0+R-1 of an [.., n] tensor: fresh, or that byte range of bufs[name]
-        (4-row groups: r0 and R multiples of 4)."""
-        if bufs is None:
-            return _ops.mask4_empty(R, n, dev)
-        off = (r0 // 4) * ((n + 3) // 4) * 4
-        return bufs[name][off:off + _ops.mask4_bytes(R, n)]
-
-    def _gemm_bwd(self, *args, **kw):
-        """A backward GEMM that may overlap the bucket all-reduce (launch mode: self.shared_cus)."""
-        return _ops.gemm(*args, shared_cus=self.shared_cus, **kw)
+        return _ops.gemm(a, b, c, m, n, k, lda, ldb, ldc, split_k=split, workspace=self._split_ws(split, m, n), **kw)
 
     def _head_gemm(self, a, b, c, m, n, k, lda, ldb, ldc, **kw):
         split = head_split_for(m, n, k)
-        ws = self._workspace(split * m * n * 4) if split > 1 else None
-        _ops.gemm(a, b, c, m, n, k, lda, ldb, ldc, split_k=split, workspace=ws, **kw)
+        _ops.gemm(a, b, c, m, n, k, lda, ldb, ldc, split_k=split, workspace=self._split_ws(split, m, n), **kw)
 
     def _head_linear(self, x, w, bias):
         m, k = x.shape
@@ -430,9 +414,6 @@ class Engine:
         y = torch.empty(m, n, dtype=x.dtype, device=x.device)
         self._head_gemm(x, w, y, m, n, k, x.stride(0), w.stride(0), n, bias=bias)
         return y
-
-    def _colsum(self, x, rows, cols, ld, out, beta, alpha=1.0):
-        _ops.colsum(x, rows, cols, ld, out, beta=beta, alpha=alpha)
 
     def _attach_grads(self):
         """Expose the flat gradient buffer as param.grad of every parameter that requires grad (frozen ones keep
@@ -488,11 +469,8 @@ class Engine:
         x = x.contiguous()
         if x.dtype not in (torch.float32, torch.bfloat16):
             x = x.float()
-        D, T, N, L, dt = self.D, self.T, self.N, self.L, self.dtype
-        M = B * T
-        es = 2 if dt == torch.bfloat16 else 4
+        D, T, L, dt = self.D, self.T, self.L, self.dtype
         prm = self.params
-        mk = self._mark
         seed = dropout_seed(int(torch.randint(0, 2 ** 31 - 1, (1,)).item()), self.dropout_rank) if training else 0
         tape = Tape() if save else None
 
@@ -503,15 +481,16 @@ class Engine:
         # gradients as computing all B*T rows and discarding the rest.  `prune_last = False` computes every row.
         prune = self.prune_last
         nc = self.fwd_streams
-        cols = torch.empty(B * N, self.CPP, dtype=dt, device=x.device)
-        xcur = torch.empty(M, D, dtype=dt, device=x.device)
+        cols = torch.empty(B * self.N, self.CPP, dtype=dt, device=x.device)
+        xcur = torch.empty(B * T, D, dtype=dt, device=x.device)
         if (nc > 1 and not want_probs and self.profile_hook is None and B % (4 * nc) == 0
                 and ((B // nc) * T) % 4 == 0):
             xcur = self._forward_blocks_split(x, cols, xcur, B, training, seed, save, prune, blocks, nc)
         else:
             self._embed(x, cols, xcur, 0, B)
             for l in range(L):
-                xcur, saved = self.block_forward(l, xcur, B, training, seed, save, want_probs, prune and l == L - 1)
+                xcur, saved = self.block_forward(l, xcur, B, training, seed, save, want_probs,
+                                                 pr=prune and l == L - 1)
                 if save:
                     blocks.append(saved)
         # classifier on token 0 (= first PATCH, vit.py:80): Linear -> GELU(erf) -> LayerNorm(4D) -> Linear, fp32
@@ -531,24 +510,26 @@ class Engine:
             tape.row0 = prune and self.row0_attention and not want_probs
         return logits, tape
 
-    def _block_bufs(self, B, training, save, dev):
-        """Whole-batch outputs of one (unpruned) block for the two-stream forward: the tensors block_forward would
-        allocate."""
+    def _block_bufs(self, x_in, B, training, save, pr=False, q0only=False):
+        """Every tensor the forward of one block writes for the B images of x_in: (BlockActs, x_out).  The only place
+        that says which exist and how large they are.  `pr` (the pruned last block): the post-attention tensors and
+        masks on the B token-0 rows; `q0only`: its attention runs on query 0 alone (no fp32 O).  The masks exist only
+        where a backward will read them: hm (ReLU) on a saving forward, pm / fm (dropout keep bits) on a saving
+        training one; o32 where the attention backward at this shape takes it."""
         D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
         M = B * T
+        R = B if pr else M
+        dev = x_in.device
         e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)   # noqa: E731
         f32 = torch.float32
-        b = {"a1": e(M, D), "m1": e(M, dtype=f32), "r1": e(M, dtype=f32), "qkv": e(M, 3 * D), "o": e(M, D),
-             "lse": e(B, H, T, dtype=f32), "x_mid": e(M, D), "a2": e(M, D), "m2": e(M, dtype=f32),
-             "r2": e(M, dtype=f32), "h": e(M, 4 * D), "x_out": e(M, D)}
-        if save and _ops.attn_bwd_uses_o32(B, T, H, hd, dt):
-            b["o32"] = e(M, D, dtype=f32)
-        if save and training:
-            b["pm"] = _ops.mask4_empty(M, D, dev)
-            b["fm"] = _ops.mask4_empty(M, D, dev)
-        if save:
-            b["hm"] = _ops.mask4_empty(M, 4 * D, dev)
-        return b
+        acts = BlockActs(
+            x_in=x_in, a1=e(M, D), m1=e(M, dtype=f32), r1=e(M, dtype=f32), qkv=e(M, 3 * D), o=e(M, D),
+            o32=e(M, D, dtype=f32) if save and not q0only and _ops.attn_bwd_uses_o32(B, T, H, hd, dt) else None,
+            lse=e(B, H, T, dtype=f32), x_mid=e(R, D), a2=e(R, D), m2=e(R, dtype=f32), r2=e(R, dtype=f32),
+            h=e(R, 4 * D), hm=_ops.mask4_empty(R, 4 * D, dev) if save else None,
+            pm=_ops.mask4_empty(R, D, dev) if save and training else None,
+            fm=_ops.mask4_empty(R, D, dev) if save and training else None)
+        return acts, e(R, D)
 
     def _embed(self, x, cols, xcur, b0, B):
         """Patch embedding (vit.py:21-29, 39-42) of images b0 .. b0+B-1 into their rows of the whole-batch cols /
@@ -573,7 +554,7 @@ class Engine:
         independent; dropout indices are the whole batch's), so the outputs are bitwise the same; the chains fill
         each other's idle CUs.  The blocks' outputs are whole-batch buffers allocated on the current stream and
         recorded on every chain stream."""
-        D, T, L = self.D, self.T, self.L
+        T, L = self.T, self.L
         dev = xcur.device
         cur = torch.cuda.current_stream(dev)
         if self._fwd_pair is None or len(self._fwd_pair) != nc or self._fwd_pair[0].device != dev:
@@ -582,13 +563,17 @@ class Engine:
         for st in streams:
             st.wait_stream(cur)
         Bh, Mh = B // nc, (B // nc) * T
-        for t in (x, cols, xcur):
-            for st in streams:
-                t.record_stream(st)
+
+        def on_chains(tensors):
+            for t in tensors:
+                if t is not None:
+                    for st in streams:
+                        t.record_stream(st)
+
+        on_chains((x, cols, xcur))
         for i, st in enumerate(streams):
             with torch.cuda.stream(st):
                 self._embed(x, cols, xcur, i * Bh, Bh)
-        names = ("a1", "m1", "r1", "qkv", "o", "o32", "lse", "x_mid", "a2", "m2", "r2", "h", "hm", "pm", "fm")
         # the ring attention forward of one chain on 3/4 of the CUs, so the other chain's GEMMs run beside it instead
         # of waiting for the whole latency-bound kernel (one box, interleaved: 30.50 -> 30.19 ms/step; 1/2 and 7/8 of
         # the CUs gain less) — unless the caller set the attn_fwd_grid option itself.  Passed per call (vit_attn_fwd's
@@ -596,7 +581,6 @@ class Engine:
         wgs = 0
         if _lib.get_option("attn_fwd_grid") == 0:
             wgs = max(1, torch.cuda.get_device_properties(dev).multi_processor_count * 3 // 4)
-        self._split_fwd = True
         # the pruned last block runs whole-batch after the join: split, its B token-0 rows would become two GEMMs of
         # B/2 rows (below the 256-row tile: the slow small-M kernels)
         nsplit = L - 1 if prune else L
@@ -604,157 +588,135 @@ class Engine:
         # reads and writes only its own rows, in order on its own stream, so block l + 2 may overwrite block l's rows
         # of a chain once that chain's block l + 1 consumed them (fresh sets per block, each recorded on
         # both streams, let the caching allocator hold up to L blocks of activations while the host runs ahead)
-        ping = None if save else [self._block_bufs(B, training, save, dev) for _ in range(2)]
-        for t in ([xcur] if save else [xcur] + [t for bs in ping for t in bs.values()]):
-            for st in streams:
-                t.record_stream(st)
-        try:
-            for l in range(nsplit):
-                if save:
-                    bufs = self._block_bufs(B, training, save, dev)
-                    for t in bufs.values():
-                        for st in streams:
-                            t.record_stream(st)
-                else:
-                    bufs = ping[l % 2]
+        ping = None if save else [self._block_bufs(xcur, B, training, save) for _ in range(2)]
+        for acts, x_out in ping or ():
+            on_chains((*acts, x_out))
+        for l in range(nsplit):
+            if save:
+                acts, x_out = self._block_bufs(xcur, B, training, save)
+                on_chains((*acts, x_out))
+            else:
+                acts, x_out = ping[l % 2]
+                acts = acts._replace(x_in=xcur)
+            for i, st in enumerate(streams):
+                with torch.cuda.stream(st):
+                    part = acts.images(i * Bh, Bh, T)
+                    self.block_forward(l, part.x_in, Bh, training, seed, save, out=(part, x_out[i * Mh:(i + 1) * Mh]),
+                                       row0=i * Mh, attn_wgs=wgs)
+            if save:
+                blocks.append(acts)
+            xcur = x_out
+        if nsplit < L:
+            q0only = self.row0_attention
+            acts, x_out = self._block_bufs(xcur, B, training, save, True, q0only)
+            whole = (acts.x_in, acts.a1, acts.m1, acts.r1, acts.qkv)
+            if q0only:
+                # the pruned block's ln1 and K / V GEMM are whole-row work: per chain too
+                on_chains(whole)
                 for i, st in enumerate(streams):
                     with torch.cuda.stream(st):
-                        self.block_forward(l, xcur[i * Mh:(i + 1) * Mh], Bh, training, seed, save, False, False,
-                                           bufs=bufs, b0=i * Bh, attn_wgs=wgs)
-                if save:
-                    blocks.append((xcur,) + tuple(bufs.get(n) for n in names))
-                xcur = bufs["x_out"]
-        finally:
-            self._split_fwd = False
-        pre = None
-        if nsplit < L and self.row0_attention:
-            # the pruned block's ln1 and K / V GEMM are whole-row work: per chain too
-            l = L - 1
-            D = self.D
-            pre = (torch.empty(B * T, D, dtype=self.dtype, device=dev),
-                   torch.empty(B * T, dtype=torch.float32, device=dev),
-                   torch.empty(B * T, dtype=torch.float32, device=dev),
-                   torch.empty(B * T, 3 * D, dtype=self.dtype, device=dev))
-            for t in pre:
-                for st in streams:
-                    t.record_stream(st)
-            wq = self.ww[f"{l}.qkv_w"]
-            for i, st in enumerate(streams):
-                r = slice(i * Mh, (i + 1) * Mh)
-                with torch.cuda.stream(st):
-                    _ops.layernorm_fwd(xcur[r], self.params[f"{l}.ln1_w"], self.params[f"{l}.ln1_b"], eps=LN_EPS,
-                                       y=pre[0][r], mean=pre[1][r], rstd=pre[2][r])
-                    _ops.gemm(pre[0][r], wq[D:], pre[3][r][:, D:], Mh, 2 * D, D, D, D, 3 * D)
+                        self._ln1_qkv(L - 1, *(t[i * Mh:(i + 1) * Mh] for t in whole), True)
         for st in streams:
             cur.wait_stream(st)
         if nsplit < L:
-            xcur, saved = self.block_forward(L - 1, xcur, B, training, seed, save, False, True, pre=pre)
+            if not q0only:
+                self._ln1_qkv(L - 1, *whole, False)
+            xcur = self._attend_ffn(L - 1, acts, x_out, B, training, seed, save, False, True, q0only)
             if save:
-                blocks.append(saved)
+                blocks.append(acts)
         return xcur
 
-    def block_forward(self, l, x_in, B, training, seed, save, want_probs=False, pr=False, bufs=None, b0=0,
-                      pre=None, attn_wgs=0):
+    def block_forward(self, l, x_in, B, training, seed, save, want_probs=False, *, pr=False, out=None, row0=0,
+                      attn_wgs=0):
         """Block l (transformer.py:76-79) on x_in [B*T, D] (compute dtype): x_mid = x_in + drop(MHA(ln1(x_in))),
         x_out = x_mid + drop(FFN(ln2(x_mid))).  `pr`: the post-attention part on the B token-0 rows only (the pruned
-        last block).  Returns (x_out, saved): `saved` is what block_backward needs (None unless `save`).
-        `bufs` (the two-stream forward, _forward_blocks_split): the block's outputs for the whole batch, preallocated;
-        this call is images b0 .. b0+B-1 of it and writes their rows (dropout bits drawn at the whole batch's
-        indices), saved = None.  `pre` (the pruned block after the two-chain forward): its ln1 output / statistics and
-        qkv with the K / V columns already computed per chain; only the token-0 rows' Q GEMM is left."""
-        model = self.model_ref()
+        last block).  Returns (x_out, saved): `saved` is the BlockActs block_backward needs (None unless `save`).
+        `out` (the two-stream forward, _forward_blocks_split): the (BlockActs, x_out) to write into instead of fresh
+        ones — a row range (BlockActs.images) of the whole batch's, x_in being its row `row0`: the dropout bits are
+        drawn at the whole batch's indices."""
+        q0only = pr and self.row0_attention and not want_probs  # the pruned block's attention on query 0 alone
+        a, x_out = out if out is not None else self._block_bufs(x_in, B, training, save, pr, q0only)
+        self._ln1_qkv(l, a.x_in, a.a1, a.m1, a.r1, a.qkv, q0only)
+        self._attend_ffn(l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0, attn_wgs)
+        return x_out, a if save else None
+
+    def _ln1_qkv(self, l, x_in, a1, m1, r1, qkv, kv_only):
+        """The part of block l before its attention that is whole-row work: a1 = ln1(x_in), then qkv = a1 Wqkv^T —
+        `kv_only` (the pruned block with the query-0 attention): its K / V columns D..3D only; _attend_ffn adds Q of
+        the token-0 rows, the only Q rows that attention reads."""
+        D = self.D
+        M = x_in.shape[0]
+        es = 2 if self.dtype == torch.bfloat16 else 4
+        mk = self._mark
+        wq = self.ww[f"{l}.qkv_w"]
+        mk("ln_fwd", 0, 0.0, 2 * M * D * es + 8 * M)
+        _ops.layernorm_fwd(x_in, self.params[f"{l}.ln1_w"], self.params[f"{l}.ln1_b"], eps=LN_EPS, y=a1, mean=m1,
+                           rstd=r1)
+        mk("ln_fwd", 1)
+        if kv_only:
+            mk("gemm_fwd", 0, 2.0 * M * 2 * D * D, (M * D + 2 * D * D + 2 * M * D) * es)
+            _ops.gemm(a1, wq[D:], qkv[:, D:], M, 2 * D, D, D, D, 3 * D)
+        else:
+            mk("gemm_fwd", 0, 2.0 * M * 3 * D * D, (M * D + 3 * D * D + 3 * M * D) * es)
+            _ops.gemm(a1, wq, qkv, M, 3 * D, D, D, D, 3 * D)
+        mk("gemm_fwd", 1)
+
+    def _attend_ffn(self, l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0=0, attn_wgs=0):
+        """The rest of block l's forward from _ln1_qkv's a.a1 / a.qkv: attention, proj + residual, ln2, FFN +
+        residual into x_out (arguments as block_forward's); returns x_out."""
         D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
         M = B * T
         es = 2 if dt == torch.bfloat16 else 4
         prm = self.params
         mk = self._mark
         drop_p = DROPOUT_P if training else 0.0
-        keep_masks = save and training          # the backward reads the forward's dropout keep bits (mask4)
-        dev = x_in.device
-        blk = model.transformer_encoder.blocks[l]
-        ln_b = 2 * M * D * es + 8 * M
-        mk("ln_fwd", 0, 0.0, ln_b)
-        rows = self._rows_of(bufs, b0, B, T)                  # this call's slice of a whole-batch buffer
-        q0only = pr and self.row0_attention and not want_probs  # the pruned block's attention on query 0 alone
-        wq = self.ww[f"{l}.qkv_w"]
-        if pre is not None:
-            a1, m1, r1, qkv = pre
-            mk("ln_fwd", 1)
-        else:
-            a1, m1, r1 = _ops.layernorm_fwd(x_in, prm[f"{l}.ln1_w"], prm[f"{l}.ln1_b"], eps=LN_EPS,
-                                            y=rows("a1"), mean=rows("m1"), rstd=rows("r1"))
-            mk("ln_fwd", 1)
-        if q0only:
-            # ... which reads Q of the token-0 rows only: K / V of every row (one GEMM into columns D..3D), Q of the
-            # B token-0 rows (split-K over the idle CUs); the other Q rows of qkv are never read
-            if pre is None:
-                qkv = rows("qkv") if bufs is not None else torch.empty(M, 3 * D, dtype=dt, device=dev)
-                mk("gemm_fwd", 0, 2.0 * M * 2 * D * D, (M * D + 2 * D * D + 2 * M * D) * es)
-                _ops.gemm(a1, wq[D:], qkv[:, D:], M, 2 * D, D, D, D, 3 * D)
-                mk("gemm_fwd", 1)
-            mk("gemm_fwd", 0, 2.0 * B * D * D, (2 * B * D + D * D) * es)
-            self._gemm_rows(True, a1, wq, qkv, B, D, D, T * D, D, T * 3 * D)
-            mk("gemm_fwd", 1)
-        else:
-            mk("gemm_fwd", 0, 2.0 * M * 3 * D * D, (M * D + 3 * D * D + 3 * M * D) * es)
-            qkv = _ops.linear(a1, wq) if bufs is None else _ops.gemm(a1, wq, rows("qkv"), M, 3 * D, D, D, D, 3 * D)
-            mk("gemm_fwd", 1)
+        blk = self.model_ref().transformer_encoder.blocks[l]
         probs = None
         if want_probs:
-            probs = torch.empty(B, H, T, T, dtype=torch.float32, device=dev)
+            probs = torch.empty(B, H, T, T, dtype=torch.float32, device=x_out.device)
         if q0only:
+            # ... which reads Q of the token-0 rows only (split-K over the idle CUs); the other Q rows of qkv are
+            # never read
+            mk("gemm_fwd", 0, 2.0 * B * D * D, (2 * B * D + D * D) * es)
+            self._gemm_rows(True, a.a1, self.ww[f"{l}.qkv_w"], a.qkv, B, D, D, T * D, D, T * 3 * D)
+            mk("gemm_fwd", 1)
             # the pruned last block: only attention output row 0 of every image is read (the classifier reads token 0,
             # everything after the attention is per token), and every softmax row is independent -> query 0 alone,
             # O(T hd) per (image, head); o rows b*T and lse[:, :, 0] are written
-            o32 = None
             mk("attn_fwd", 0, 4.0 * B * H * T * hd, 2 * M * D * es + 2 * B * D * es + 4 * B * H)
-            o, lse = _ops.attn_fwd_row0(qkv, B, T, H, hd, self.scale, o=rows("o"), lse=rows("lse"))
+            _ops.attn_fwd_row0(a.qkv, B, T, H, hd, self.scale, o=a.o, lse=a.lse)
             mk("attn_fwd", 1)
         else:
-            # training forward in bf16 with the tiled (T > 256) backward: also keep O unrounded for its exact delta;
-            # the fused T <= 256 backward forms delta from P and dP itself (vit_hip.h)
-            o32 = None
-            if save and _ops.attn_bwd_uses_o32(B, T, H, hd, dt):
-                o32 = rows("o32") if bufs is not None else torch.empty(M, D, dtype=torch.float32, device=dev)
-            mk("attn_fwd", 0, 4.0 * B * H * T * T * hd, 4 * M * D * es + 4 * B * H * T + (4 * M * D if o32 is not None
+            # a.o32 (training forward in bf16 with the tiled T > 256 backward): also keep O unrounded for its exact
+            # delta; the fused T <= 256 backward forms delta from P and dP itself (vit_hip.h)
+            mk("attn_fwd", 0, 4.0 * B * H * T * T * hd, 4 * M * D * es + 4 * B * H * T + (4 * M * D if a.o32 is not None
                                                                                          else 0))
-            o, lse = _ops.attn_fwd(qkv, B, T, H, hd, self.scale, o=rows("o"), lse=rows("lse"), probs=probs, o32=o32,
-                                   max_wgs=attn_wgs)
+            _ops.attn_fwd(a.qkv, B, T, H, hd, self.scale, o=a.o, lse=a.lse, probs=probs, o32=a.o32, max_wgs=attn_wgs)
             mk("attn_fwd", 1)
         blk.multi_head.attention_probs = probs
         blk.multi_head._probs_skipped = probs is None       # a later read warns once (transformer.py)
         # rows of the post-attention part: all M, or (last block, pruned) the B token-0 rows b*T
         R, rs = (B, T) if pr else (M, 1)
-        r0 = b0 if pr else b0 * T                                     # this call's first row of the whole batch
-        pm = self._mask4_out(bufs, "pm", r0, R, D, dev) if keep_masks else None      # proj dropout keep bits
-        fm = self._mask4_out(bufs, "fm", r0, R, D, dev) if keep_masks else None      # fc2 dropout keep bits
-        x_mid = rows("x_mid", pr) if bufs is not None else torch.empty(R, D, dtype=dt, device=dev)
         mk("gemm_fwd", 0, 2.0 * R * D * D, (3 * R * D + D * D) * es)
-        self._gemm_rows(pr, o, self.ww[f"{l}.proj_w"], x_mid, R, D, D, rs * D, D, D, bias=prm[f"{l}.proj_b"],
-                        res=x_in, ldres=rs * D, dropout_p=drop_p, seed=site_seed(seed, l, 0),
-                        drop_row_stride=rs, mask_out=pm, drop_row0=r0)
+        self._gemm_rows(pr, a.o, self.ww[f"{l}.proj_w"], a.x_mid, R, D, D, rs * D, D, D, bias=prm[f"{l}.proj_b"],
+                        res=a.x_in, ldres=rs * D, dropout_p=drop_p, seed=site_seed(seed, l, 0),
+                        drop_row_stride=rs, mask_out=a.pm, drop_row0=row0)
         mk("gemm_fwd", 1)
         mk("ln_fwd", 0, 0.0, 2 * R * D * es + 8 * R)
-        a2, m2, r2 = _ops.layernorm_fwd(x_mid, prm[f"{l}.ln2_w"], prm[f"{l}.ln2_b"], eps=LN_EPS,
-                                        y=rows("a2", pr), mean=rows("m2", pr), rstd=rows("r2", pr))
+        _ops.layernorm_fwd(a.x_mid, prm[f"{l}.ln2_w"], prm[f"{l}.ln2_b"], eps=LN_EPS, y=a.a2, mean=a.m2, rstd=a.r2)
         mk("ln_fwd", 1)
-        # saved for the backward: the ReLU mask as 1 bit per element (mask4, read by fc2's dgrad epilogue instead
-        # of re-reading h: 1/16 of the bytes)
-        hm = self._mask4_out(bufs, "hm", r0, R, 4 * D, dev) if save else None
+        # a.hm, saved for the backward: the ReLU mask as 1 bit per element (mask4, read by fc2's dgrad epilogue
+        # instead of re-reading h: 1/16 of the bytes)
         mk("gemm_fwd", 0, 2.0 * R * 4 * D * D, (R * D + 4 * D * D + 4 * R * D) * es + (R * D // 2 if save else 0))
-        h = rows("h", pr) if bufs is not None else torch.empty(R, 4 * D, dtype=dt, device=dev)
-        self._gemm_rows(pr, a2, self.ww[f"{l}.fc1_w"], h, R, 4 * D, D, D, D, 4 * D, bias=prm[f"{l}.fc1_b"],
-                        act=ACT_RELU, mask_out=hm)
+        self._gemm_rows(pr, a.a2, self.ww[f"{l}.fc1_w"], a.h, R, 4 * D, D, D, D, 4 * D, bias=prm[f"{l}.fc1_b"],
+                        act=ACT_RELU, mask_out=a.hm)
         mk("gemm_fwd", 1)
-        x_out = rows("x_out", pr) if bufs is not None else torch.empty(R, D, dtype=dt, device=dev)
         mk("gemm_fwd", 0, 2.0 * R * 4 * D * D, (4 * R * D + 4 * D * D + 2 * R * D) * es)
-        self._gemm_rows(pr, h, self.ww[f"{l}.fc2_w"], x_out, R, D, 4 * D, 4 * D, 4 * D, D, bias=prm[f"{l}.fc2_b"],
-                        res=x_mid, ldres=D, dropout_p=drop_p, seed=site_seed(seed, l, 1), drop_row_stride=rs,
-                        mask_out=fm, drop_row0=r0)
+        self._gemm_rows(pr, a.h, self.ww[f"{l}.fc2_w"], x_out, R, D, 4 * D, 4 * D, 4 * D, D, bias=prm[f"{l}.fc2_b"],
+                        res=a.x_mid, ldres=D, dropout_p=drop_p, seed=site_seed(seed, l, 1), drop_row_stride=rs,
+                        mask_out=a.fm, drop_row0=row0)
         mk("gemm_fwd", 1)
-        saved = (x_in, a1, m1, r1, qkv, o, o32, lse, x_mid, a2, m2, r2, h, hm, pm, fm) if save and bufs is None \
-            else None
-        return x_out, saved
+        return x_out
 
     # ------------------------------------------------------------------------------------------------------------
     # backward
@@ -767,23 +729,22 @@ class Engine:
             return
         a, b = rng
         bf = self.comm_dtype == torch.bfloat16
+        # RCCL: native average, issued from `side` when there is one (the main chain does not wait).  gloo (CPU tests):
+        # from the current stream, after `side`; a sum, scaled after the wait.
         nccl = dist.get_backend(self.ddp_group) == "nccl"
-        if nccl:                                          # RCCL: native average
-            if side is not None:                          # issued from `side`: the main chain does not wait
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):
-                    buf = self.G[a:b].to(torch.bfloat16) if bf else self.G[a:b]
-                    w = dist.all_reduce(buf, op=dist.ReduceOp.AVG, group=self.ddp_group, async_op=True)
+        issue_on = contextlib.nullcontext()
+        if side is not None:
+            cur = torch.cuda.current_stream(self.device)
+            if nccl:
+                side.wait_stream(cur)
+                issue_on = torch.cuda.stream(side)
             else:
-                buf = self.G[a:b].to(torch.bfloat16) if bf else self.G[a:b]
-                w = dist.all_reduce(buf, op=dist.ReduceOp.AVG, group=self.ddp_group, async_op=True)
-            self._works.append((w, rng, buf if bf else None, False))
-        else:                                             # gloo (CPU tests): sum, scaled after the wait
-            if side is not None:
-                torch.cuda.current_stream(self.device).wait_stream(side)
+                cur.wait_stream(side)
+        with issue_on:
             buf = self.G[a:b].to(torch.bfloat16) if bf else self.G[a:b]
-            w = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.ddp_group, async_op=True)
-            self._works.append((w, rng, buf if bf else None, True))
+            w = dist.all_reduce(buf, op=dist.ReduceOp.AVG if nccl else dist.ReduceOp.SUM, group=self.ddp_group,
+                                async_op=True)
+        self._works.append((w, rng, buf if bf else None, not nccl))
 
     def _finish_buckets(self):
         if not self._works:
@@ -843,8 +804,7 @@ class Engine:
         below = tape.x_grad or any(req[k] for k in ("conv_w", "conv_b", "cls", "pos"))
         need_from = {}
         for l in range(L):
-            below = below or any(req[f"{l}.{n}"] for n in ("qkv_w", "proj_w", "proj_b", "fc1_w", "fc1_b", "fc2_w",
-                                                           "fc2_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b"))
+            below = below or any(req[f"{l}.{n}"] for n in BLOCK_REGIONS)
             need_from[l] = below
         dev = dlogits.device
         dlogits = dlogits.contiguous().float()
@@ -856,18 +816,18 @@ class Engine:
         if req["h3_w"]:
             self._wgrad(dlogits, tape.zn, gw["h3_w"], nc, 4 * D, B, nc, 4 * D, beta, side)
         if req["h3_b"]:
-            self._colsum(dlogits, B, nc, nc, gw["h3_b"], beta)
+            _ops.colsum(dlogits, B, nc, nc, gw["h3_b"], beta=beta)
         dgz = torch.empty_like(tape.gz)
         part = _ops.layernorm_bwd(dzn, tape.gz, prm["hln_w"], tape.mh, tape.rh, dgz)
-        self._colsum(part[0], part.shape[1], 4 * D, 4 * D, gw["hln_w"], beta)
-        self._colsum(part[1], part.shape[1], 4 * D, 4 * D, gw["hln_b"], beta)
+        _ops.colsum(part[0], part.shape[1], 4 * D, 4 * D, gw["hln_w"], beta=beta)
+        _ops.colsum(part[1], part.shape[1], 4 * D, 4 * D, gw["hln_b"], beta=beta)
         du = _ops.gelu_bwd(tape.u, dgz)
         dz = torch.empty(B, D, dtype=torch.float32, device=dev)
         self._head_gemm(du, prm["h0_w"], dz, B, D, 4 * D, 4 * D, D, D, b_kcontig=False)
         if req["h0_w"]:
             self._wgrad(du, tape.z, gw["h0_w"], 4 * D, D, B, 4 * D, D, beta, side)
         if req["h0_b"]:
-            self._colsum(du, B, 4 * D, 4 * D, gw["h0_b"], beta)
+            _ops.colsum(du, B, 4 * D, 4 * D, gw["h0_b"], beta=beta)
         self._bucket_ready(self.head_range, side)
         if not need_from[L - 1]:
             if side is not None:
@@ -885,14 +845,14 @@ class Engine:
         # (GEMM alpha, column-sum alpha, the LN kernels' bias-gradient sums) instead of a rounding of its own.  The
         # keep bits are the ones the forward's GEMM epilogues saved (mask4), not a re-hash (block_backward).
         if tape.training:
-            g1 = _ops.mask4_apply(dx, torch.empty_like(dx), tape.blocks[L - 1][15], 1.0)
+            g1 = _ops.mask4_apply(dx, torch.empty_like(dx), tape.blocks[L - 1].fm, 1.0)
         else:
             g1 = dx
         g1_summed = False          # block L-1's fc2 bias gradient: g1 comes from the head (plain column sum below)
         for l in reversed(range(L)):
             if not need_from[l]:
                 break
-            prev_mask = tape.blocks[l - 1][15] if (tape.training and l > 0) else None
+            prev_mask = tape.blocks[l - 1].fm if (tape.training and l > 0) else None
             dx, g1n = self.block_backward(l, tape.blocks[l], dx, g1, g1_summed, beta, req, side, tape.training, B,
                                           pruned and l == L - 1, chain_prev=l > 0, prev_mask=prev_mask,
                                           row0=tape.row0 and l == L - 1)
@@ -905,11 +865,11 @@ class Engine:
             if req["cls"]:
                 _ops.copy2d(dx[N:], T * D, gw["cls"].view(B, D), D, B, D, beta=beta)       # CLS row of every image
             if req["pos"]:
-                self._colsum(dx, B, T * D, T * D, gw["pos"].view(-1), beta)                 # pos: sum over the batch
+                _ops.colsum(dx, B, T * D, T * D, gw["pos"].view(-1), beta=beta)            # pos: sum over the batch
             dpatch = torch.empty(B * N, D, dtype=dt, device=dev)
             _ops.copy2d(dx, D, dpatch, D, B * N, D, group=(N, T))
             if req["conv_b"]:
-                self._colsum(dpatch, B * N, D, D, gw["conv_b"], beta)
+                _ops.colsum(dpatch, B * N, D, D, gw["conv_b"], beta=beta)
             if req["conv_w"]:
                 self._wgrad(dpatch, tape.cols, gw["conv_w"], D, self.CPP, B * N, D, self.CPP, beta, side,
                             "gemm_wgrad")
@@ -926,15 +886,16 @@ class Engine:
         self._attach_pending()
         return dimg
 
-    def block_backward(self, l, saved, dx, g1, g1_summed, beta, req, side, training, B, pr=False, chain_prev=False,
+    def block_backward(self, l, acts, dx, g1, g1_summed, beta, req, side, training, B, pr=False, chain_prev=False,
                        prev_mask=None, row0=None):
-        """Backward of block l from d(x_out) = dx and g1 = the fc2-dropout-masked dx (dx itself in eval).  Writes the
-        block's weight gradients into the flat buffer (beta: 0 overwrite / 1 accumulate; req: which regions want a
-        gradient) and returns (dx_in, g1n).  `chain_prev`: there is a block l-1 below, so the ln1 backward also emits
-        block l-1's fc2 bias-gradient column sums and — in training, from its keep bits `prev_mask` — g1n, the next
-        block's masked gradient (None otherwise).  `g1_summed`: this block's fc2 bias gradient was already summed by
-        the block above.  `pr`: the pruned last block (dx / g1 are its B token-0 rows).  `row0`: its forward ran the
-        query-0 attention (Tape.row0; None: pr and self.row0_attention, for direct callers)."""
+        """Backward of block l (`acts`: its forward's BlockActs) from d(x_out) = dx and g1 = the fc2-dropout-masked dx
+        (dx itself in eval).  Writes the block's weight gradients into the flat buffer (beta: 0 overwrite / 1
+        accumulate; req: which regions want a gradient) and returns (dx_in, g1n).  `chain_prev`: there is a block l-1
+        below, so the ln1 backward also emits block l-1's fc2 bias-gradient column sums and — in training, from its
+        keep bits `prev_mask` — g1n, the next block's masked gradient (None otherwise).  `g1_summed`: this block's fc2
+        bias gradient was already summed by the block above.  `pr`: the pruned last block (dx / g1 are its B token-0
+        rows).  `row0`: its forward ran the query-0 attention (Tape.row0; None: pr and self.row0_attention, for
+        direct callers)."""
         if row0 is None:
             row0 = pr and self.row0_attention
         D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
@@ -946,22 +907,21 @@ class Engine:
         dev = dx.device
         gs = 1.0 / (1.0 - DROPOUT_P) if training else 1.0
         R, rs = (B, T) if pr else (M, 1)
-        x_in, a1, m1, r1, qkv, o, o32, lse, x_mid, a2, m2, r2, h, hm, pm, fm = saved
         # FFN: x_out = x_mid + drop(relu(ln2(x_mid) W1^T + b1) W2^T + b2)
         if req[f"{l}.fc2_w"]:
-            self._wgrad(g1, h, gw[f"{l}.fc2_w"], D, 4 * D, R, D, 4 * D, beta, side, "gemm_wgrad", alpha=gs)
+            self._wgrad(g1, acts.h, gw[f"{l}.fc2_w"], D, 4 * D, R, D, 4 * D, beta, side, "gemm_wgrad", alpha=gs)
         if not g1_summed:
-            self._colsum(g1, R, D, D, gw[f"{l}.fc2_b"], beta, alpha=gs)
+            _ops.colsum(g1, R, D, D, gw[f"{l}.fc2_b"], beta=beta, alpha=gs)
         dh = torch.empty(R, 4 * D, dtype=dt, device=dev)
         dh_part = torch.empty(_ops.colsum_part_rows(R), 4 * D, dtype=torch.float32, device=dev)
         # relu backward and the fc1 bias-gradient column sums fused into the dgrad epilogue
         mk("gemm_dgrad", 0, 2.0 * R * 4 * D * D, (R * D + 4 * D * D + 4 * R * D) * es + R * D // 2)
-        self._gemm_rows(pr, g1, self.ww[f"{l}.fc2_w"], dh, R, 4 * D, D, D, 4 * D, 4 * D, b_kcontig=False, aux=hm,
+        self._gemm_rows(pr, g1, self.ww[f"{l}.fc2_w"], dh, R, 4 * D, D, D, 4 * D, 4 * D, b_kcontig=False, aux=acts.hm,
                         colsum_part=dh_part, alpha=gs, shared_cus=self.shared_cus)
         mk("gemm_dgrad", 1)
         cs_jobs = [(dh_part, [gw[f"{l}.fc1_b"]], beta)]      # this block's bias / LN-affine sums: one launch below
         if req[f"{l}.fc1_w"]:
-            self._wgrad(dh, a2, gw[f"{l}.fc1_w"], 4 * D, D, R, 4 * D, D, beta, side, "gemm_wgrad")
+            self._wgrad(dh, acts.a2, gw[f"{l}.fc1_w"], 4 * D, D, R, 4 * D, D, beta, side, "gemm_wgrad")
         da2 = torch.empty(R, D, dtype=dt, device=dev)
         mk("gemm_dgrad", 0, 2.0 * R * 4 * D * D, (4 * R * D + 4 * D * D + R * D) * es)
         self._gemm_rows(pr, dh, self.ww[f"{l}.fc1_w"], da2, R, D, 4 * D, 4 * D, D, D, b_kcontig=False,
@@ -972,15 +932,15 @@ class Engine:
         # ln2 backward + residual add + dropout backward of the MHA branch; its third partial set is the column
         # sums of g0 as stored = the proj bias gradient
         mk("ln_bwd", 0, 0.0, (3 + 1 + (g0 is not None)) * R * D * es + 8 * R + R * D // 8)
-        part = _ops.layernorm_bwd(da2, x_mid, prm[f"{l}.ln2_w"], m2, r2, dx_mid, dres=dx, drop_out=g0,
-                                  drop_p=DROPOUT_P, drop_mask=pm, osum=True)
+        part = _ops.layernorm_bwd(da2, acts.x_mid, prm[f"{l}.ln2_w"], acts.m2, acts.r2, dx_mid, dres=dx, drop_out=g0,
+                                  drop_p=DROPOUT_P, drop_mask=acts.pm, osum=True)
         mk("ln_bwd", 1)
         cs_jobs.append((part, [gw[f"{l}.ln2_w"], gw[f"{l}.ln2_b"], gw[f"{l}.proj_b"]], beta))
         if g0 is None:
             g0 = dx_mid
         # MHA: x_mid = x_in + drop(attn(ln1(x_in)) Wp^T + bp)
         if req[f"{l}.proj_w"]:
-            self._wgrad(g0, o, gw[f"{l}.proj_w"], D, D, R, D, rs * D, beta, side, "gemm_wgrad", alpha=gs)
+            self._wgrad(g0, acts.o, gw[f"{l}.proj_w"], D, D, R, D, rs * D, beta, side, "gemm_wgrad", alpha=gs)
         do = torch.empty(R, D, dtype=dt, device=dev)
         mk("gemm_dgrad", 0, 2.0 * R * D * D, (2 * R * D + D * D) * es)
         self._gemm_rows(pr, g0, self.ww[f"{l}.proj_w"], do, R, D, D, D, D, D, b_kcontig=False, alpha=gs,
@@ -997,7 +957,7 @@ class Engine:
             # wgrad GEMMs below
             dqkv = self._token_rows("dqkv", M, 3 * D, dt, T, dev)
             mk("attn_bwd", 0, 10.0 * B * H * T * hd, 4 * M * D * es + 4 * B * D * es + 4 * B * H)
-            _ops.attn_bwd_row0(qkv, do, D, dqkv, B, T, H, hd, self.scale)
+            _ops.attn_bwd_row0(acts.qkv, do, D, dqkv, B, T, H, hd, self.scale)
             mk("attn_bwd", 1)
         else:
             if pr:
@@ -1005,17 +965,17 @@ class Engine:
                 do_full = self._token_rows("do", M, D, dt, T, dev)
                 _ops.copy2d(do, D, do_full, T * D, B, D)
                 do = do_full
-            if o32 is None and _ops.attn_bwd_uses_o32(B, T, H, hd, dt):
+            if acts.o32 is None and _ops.attn_bwd_uses_o32(B, T, H, hd, dt):
                 # the forward chose the fused backward (no fp32 O kept) and a library option changed since: the tiled
                 # backward would form delta from the bf16 O, inexact under saturated softmax
                 raise RuntimeError("attention backward needs the fp32 O that this forward did not keep: the "
                                    "attn_bwd_split library option changed between forward and backward")
             # bytes: qkv, dO, dqkv (+ O and o32 for the tiled backward's delta pass)
-            mk("attn_bwd", 0, 10.0 * B * H * T * T * hd, 7 * M * D * es + 4 * B * H * T + (M * D * es + 4 * M * D if o32
-                                                                                          is not None else 0))
-            dqkv = _ops.attn_bwd(qkv, o, do, lse, B, T, H, hd, self.scale,
-                                 workspace=self._workspace(_ops.attn_bwd_workspace_bytes(B, T, H, hd, dt)), o32=o32,
-                                 shared_cus=self.shared_cus)
+            mk("attn_bwd", 0, 10.0 * B * H * T * T * hd,
+               7 * M * D * es + 4 * B * H * T + (M * D * es + 4 * M * D if acts.o32 is not None else 0))
+            dqkv = _ops.attn_bwd(acts.qkv, acts.o, do, acts.lse, B, T, H, hd, self.scale,
+                                 workspace=self._workspace(_ops.attn_bwd_workspace_bytes(B, T, H, hd, dt)),
+                                 o32=acts.o32, shared_cus=self.shared_cus)
             mk("attn_bwd", 1)
         wq = self.ww[f"{l}.qkv_w"]
         da1 = torch.empty(M, D, dtype=dt, device=dev)
@@ -1025,10 +985,10 @@ class Engine:
             # epilogue, in place)
             if req[f"{l}.qkv_w"]:
                 gq = gw[f"{l}.qkv_w"]
-                self._wgrad(dqkv[:, D:], a1, gq[D:], 2 * D, D, M, 3 * D, D, beta, side, "gemm_wgrad")
-                self._wgrad(dqkv, a1, gq[:D], D, D, B, T * 3 * D, T * D, beta, side, "gemm_wgrad")
+                self._wgrad(dqkv[:, D:], acts.a1, gq[D:], 2 * D, D, M, 3 * D, D, beta, side, "gemm_wgrad")
+                self._wgrad(dqkv, acts.a1, gq[:D], D, D, B, T * 3 * D, T * D, beta, side, "gemm_wgrad")
             mk("gemm_dgrad", 0, 2.0 * M * 2 * D * D, (2 * M * D + 2 * D * D + M * D) * es)
-            self._gemm_bwd(dqkv[:, D:], wq[D:], da1, M, D, 2 * D, 3 * D, D, D, b_kcontig=False)
+            _ops.gemm(dqkv[:, D:], wq[D:], da1, M, D, 2 * D, 3 * D, D, D, b_kcontig=False, shared_cus=self.shared_cus)
             mk("gemm_dgrad", 1)
             mk("gemm_dgrad", 0, 2.0 * B * D * D, (3 * B * D + D * D) * es)
             self._gemm_rows(True, dqkv, wq, da1, B, D, D, T * 3 * D, D, T * D, b_kcontig=False, res=da1,
@@ -1036,16 +996,16 @@ class Engine:
             mk("gemm_dgrad", 1)
         else:
             if req[f"{l}.qkv_w"]:
-                self._wgrad(dqkv, a1, gw[f"{l}.qkv_w"], 3 * D, D, M, 3 * D, D, beta, side, "gemm_wgrad")
+                self._wgrad(dqkv, acts.a1, gw[f"{l}.qkv_w"], 3 * D, D, M, 3 * D, D, beta, side, "gemm_wgrad")
             mk("gemm_dgrad", 0, 2.0 * M * 3 * D * D, (3 * M * D + 3 * D * D + M * D) * es)
-            self._gemm_bwd(dqkv, wq, da1, M, D, 3 * D, 3 * D, D, D, b_kcontig=False)
+            _ops.gemm(dqkv, wq, da1, M, D, 3 * D, 3 * D, D, D, b_kcontig=False, shared_cus=self.shared_cus)
             mk("gemm_dgrad", 1)
         dx_in = torch.empty(M, D, dtype=dt, device=dev)
         g1n = torch.empty(M, D, dtype=dt, device=dev) if (training and chain_prev) else None
         # ln1 backward; for l > 0 its third partial set is the column sums of the next g1 (g1n, or dx_in in eval)
         # = the fc2 bias gradient of block l-1
         mk("ln_bwd", 0, 0.0, (3 + 1 + (g1n is not None)) * M * D * es + 8 * M)
-        part = _ops.layernorm_bwd(da1, x_in, prm[f"{l}.ln1_w"], m1, r1, dx_in, dres=dx_mid, drop_out=g1n,
+        part = _ops.layernorm_bwd(da1, acts.x_in, prm[f"{l}.ln1_w"], acts.m1, acts.r1, dx_in, dres=dx_mid, drop_out=g1n,
                                   drop_p=DROPOUT_P, drop_mask=prev_mask if g1n is not None else None,
                                   osum=chain_prev)
         mk("ln_bwd", 1)
@@ -1067,9 +1027,8 @@ class Engine:
         `register_post_accumulate_grad_hook` hooks run on the parameter — each once per backward, in registration
         order.  When the backward accumulated into existing gradients, the buffer holds the increment here
         (backward() set `_acc_old`): the hooks see the increment, then the previous gradients are added back."""
-        old = getattr(self, "_acc_old", None)
-        self._acc_old = None
-        for gv, keep in getattr(self, "_frozen_keep", None) or ():
+        old, self._acc_old = self._acc_old, None
+        for gv, keep in self._frozen_keep or ():
             gv.copy_(keep)
         self._frozen_keep = None
         for p, gv in self.grad_views:
