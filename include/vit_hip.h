@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VIT_ABI_VERSION 15
+#define VIT_ABI_VERSION 16
 
 typedef enum { VIT_OK = 0, VIT_ERR_INVALID = 1, VIT_ERR_LAUNCH = 2 } vit_status;
 typedef enum { VIT_F32 = 0, VIT_BF16 = 1, VIT_MASK4 = 2 } vit_dtype;
@@ -63,14 +63,13 @@ const char* vit_last_error(void);
  *   "attn_bwd_grid"      0 (automatic): workgroups of the persistent attention backward
  *   "ln16"               1: the 16-B-per-lane LayerNorm forward where the layout allows it
  *   "ln_al"              1: LayerNorm backward accumulators in LDS (0: registers)
- *   "gemm_tail_v2"       0: 1 runs the tile rows of a last round of 256x256 tiles at most half full that the split-K
- *                        tail does not take as 128x128 tiles (two workgroups per CU) in a second launch (measured
- *                        slower at C2: 33.0 vs 31.6 ms/step)
  *   "splitk_rounds"      1: rounds of 256 workgroups the weight-gradient K split aims at (vit_gemm_split_k_hint)
  *   "attn_fwd_grid"      0 (automatic: one workgroup per CU): workgroups of the persistent ring attention forward
  *                        when the call's own max_wgs is 0
  * ABI 15 removed the one-workgroup-per-head attention forward, which lost its A/B runs, together with the option name
  * that selected it: vit_set_option refuses that name.
+ * ABI 16 removed the 128x128-tile second launch for a last partial round of 256x256 tiles, which measured slower (33.0
+ * vs 31.6 ms/step), and its option name "gemm_tail_v2": refused likewise.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);

@@ -263,11 +263,11 @@ def test_engine_roctx_ranges(monkeypatch):
 
 def test_library_options_host_only():
     """vit_set_option / vit_get_option (vit_hip.h): the documented names and shipped defaults, set/restore, and an
-    unknown name refused, the name retired with ABI 15 among them — host-side only, and the library never reads the
-    environment (no getenv in csrc/)."""
+    unknown name refused, the names retired with ABI 15 and 16 among them — host-side only, and the library never
+    reads the environment (no getenv in csrc/)."""
     defaults = {"gemm_impl": 0, "gemm_tail": 0, "gemm_tail_min_kt": 40, "splitk_min_kt": 0, "gemm_group_m": 0,
                 "gemm_epi_general": 0, "gemm_persist": 1, "attn_fwd_split": 0, "attn_bwd_split": 0,
-                "attn_bwd_grid": 0, "ln16": 1, "ln_al": 1, "gemm_tail_v2": 0,
+                "attn_bwd_grid": 0, "ln16": 1, "ln_al": 1,
                 "splitk_rounds": 1, "attn_fwd_grid": 0}
     for k, v in defaults.items():
         assert _lib.get_option(k) == v, k
@@ -278,6 +278,8 @@ def test_library_options_host_only():
         _lib.set_option("no_such_option", 1)
     with pytest.raises(RuntimeError):
         _lib.set_option("attn_fwd_ring", 1)
+    with pytest.raises(RuntimeError):
+        _lib.set_option("gemm_tail_v2", 1)
     with pytest.raises(KeyError):
         _lib.get_option("no_such_option")
     csrc = os.path.join(ROOT, "vision-transformer_amd", "csrc")

@@ -28,7 +28,8 @@ Host-dispatch branch -> the test that reaches it:
 | gemm_impl 1, 2, 4, f32 x scalar epilogue (ldc = N + 1)   | test_gemm_contract_odd_ldc, ..._scalar_aux              |
 | gemm_impl 1, 2, 4, f32 x split-K reduce, vector          | test_gemm_contract[*-l], [*-m], ..._three_full_slices   |
 | gemm_impl 1, 2, 4, f32 x split-K reduce, scalar          | test_gemm_contract_scalar_epilogue[l-*]                 |
-| gemm_tail_v2 second launch; gemm_group_m                 | test_gemm_tail_v2; test_gemm_group_m                    |
+| one-row last tile row of a partial round; gemm_group_m   | test_gemm_one_row_partial_round; test_gemm_group_m      |
+| v4 bias + GELU (LDS-image epilogue) + mask_out + colsum  | test_gemm_v4_bias_gelu_side_outputs                     |
 | vit_col2im, vit_embed_cls, vit_relu_bwd                  | test_col2im, test_embed_cls, test_relu_bwd              |
 | vit_mask4_apply, vit_pack                                | test_mask4_apply, test_pack                             |
 | vit_adamw (grad_scale, f32 / NULL shadow)                | test_adamw_grad_scale_and_shadows                       |
@@ -287,10 +288,11 @@ def test_gemm_contract_scalar_aux_ten_columns(libopt):
     _run_gemm_recipe(libopt, "f32", TF, "f", n=10)
 
 
-def _tail_v2_smallest_m(n):
-    """tail_rows_v2 (vit_gemm.hip): with tn = ceil(n / 256) tile columns it needs rounds = tm * tn // 256 >= 1 and a
-    last round tail = (tm - rounds * 256 // tn) * tn with 0 < 2 * tail <= 256; the smallest M is one row past the
-    previous tile row."""
+def _partial_round_smallest_m(n):
+    """The smallest M at which the 256x256 tiles of an [M][n] output start a last partial round of the 256 CUs: with
+    tn = ceil(n / 256) tile columns, rounds = tm * tn // 256 >= 1 whole rounds and a last round tail =
+    (tm - rounds * 256 // tn) * tn with 0 < 2 * tail <= 256 (tail_split, vit_gemm.hip); one row past the previous tile
+    row."""
     tn = -(-n // 256)
     tm = 1
     while True:
@@ -302,13 +304,13 @@ def _tail_v2_smallest_m(n):
 
 
 @pytest.mark.parametrize("recipe", ["plain", "g"])
-def test_gemm_tail_v2(libopt, recipe):
-    """Option gemm_tail_v2: N = 768 (3 tile columns) takes it from 86 tile rows on (258 tiles = one round of 256 + a
-    last round of 3), i.e. M = 85 * 256 + 1 = 21761: rows 0..21759 run as 256x256 tiles, the last row as a second
-    launch of 128x128 tiles whose dropout indices, residual, mask4 offset continue at row 21760.  Exact on integers."""
-    M, N, Kd = _tail_v2_smallest_m(768), 768, 64
+def test_gemm_one_row_partial_round(recipe):
+    """N = 768 (3 tile columns) starts a last partial round at 86 tile rows (258 tiles = one round of 256 + a last
+    round of 3), i.e. M = 85 * 256 + 1 = 21761, K = 64: a one-row last tile row, unsplit (the split-K tail is off by
+    default and K is below its minimum), whose dropout indices, residual and mask4 rows continue at row 21760.  Exact
+    on integers."""
+    M, N, Kd = _partial_round_smallest_m(768), 768, 64
     assert M == 85 * 256 + 1
-    libopt("gemm_tail_v2", 1)
     g = torch.Generator().manual_seed(21)
     A, B = _ints((M, Kd), gen=g), _ints((N, Kd), gen=g)
     C = torch.full((M, N), SENTINEL, dtype=BF, device=DEV)
@@ -325,6 +327,37 @@ def test_gemm_tail_v2(libopt, recipe):
     assert torch.equal(C, stored), float((C.double() - stored.double()).abs().max())
     valid = _mask4_valid(mask.numel(), M, N)
     assert torch.equal(mask[valid], ref_mask[valid])
+
+
+def test_gemm_v4_bias_gelu_side_outputs(libopt):
+    """bias + GELU, the one fast v4 kind that keeps the LDS-image epilogue, with both side outputs: (264, 272, 64),
+    layout kk, inputs as in recipe (d) — two tile rows, so colsum_part has a full and an 8-row block.  C is bitwise
+    the general epilogue's (option gemm_epi_general); mask_out is C > 0; each colsum_part row is the fp64 column sum
+    of C as stored over its 256-row block, to the fused column sums' gate (test_gpu_kernels.test_gemm_colsum_part)."""
+    M, N, Kd = 264, 272, 64
+    libopt("gemm_impl", 4)
+    g = torch.Generator().manual_seed(_seed("bias_gelu_side", M, N, Kd))
+    A, B = _ints((M, Kd), -1, 2, gen=g), _ints((N, Kd), -1, 2, gen=g)
+    bias = _ints((N,), -1, 2, gen=g, dtype=F32)
+    outs = []
+    for general in (0, 1):
+        libopt("gemm_epi_general", general)
+        C = torch.full((M, N), SENTINEL, dtype=BF, device=DEV)
+        mask = torch.full((_ops.mask4_bytes(M, N),), 0xAA, dtype=torch.uint8, device=DEV)
+        part = torch.full((_ops.colsum_part_rows(M), N), SENTINEL, device=DEV)
+        _ops.gemm(A, B, C, M, N, Kd, Kd, Kd, N, alpha=0.5, bias=bias, act=_ops.ACT_GELU, mask_out=mask,
+                  colsum_part=part)
+        outs.append((C, mask, part))
+    torch.cuda.synchronize()
+    C, mask, part = outs[0]
+    assert torch.equal(C, outs[1][0])
+    valid = _mask4_valid(mask.numel(), M, N)
+    assert torch.equal(mask[valid], _mask4_pack(C > 0)[valid])
+    assert part.shape[0] == 2
+    for blk in range(part.shape[0]):
+        cb = C[256 * blk:256 * (blk + 1)].double()
+        err = (part[blk].double() - cb.sum(0)).abs()
+        assert bool((err <= 1e-5 * cb.abs().sum(0) + 1e-5).all()), (blk, float(err.max()))
 
 
 @pytest.mark.parametrize("group_m", [1, 3])

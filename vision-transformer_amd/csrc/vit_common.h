@@ -91,7 +91,8 @@ VIT_DEV uint32_t vit_hash_u32(uint32_t seed, uint32_t idx) {
 // byte, and over 4 consecutive rows a whole dword.
 VIT_DEV int64_t mask4_byte(int64_t i, int64_t j, int64_t n) { return (((i >> 2) * ((n + 3) >> 2)) + (j >> 2)) * 4 + (i & 3); }
 
-VIT_DEV uint32_t vit_drop_threshold(float p) {
+// Dropout drops an element when its hash is below this threshold (host-side: the launchers pass it to the kernels).
+static inline uint32_t vit_drop_threshold(float p) {
   double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
 }
@@ -132,7 +133,6 @@ void colsum_parts_launch(const void* x, int64_t ldx, int dtype, int64_t rows, in
   X(OPT_GEMM_IMPL, "gemm_impl", 0)                  \
   X(OPT_GEMM_TAIL, "gemm_tail", 0)                  \
   X(OPT_GEMM_TAIL_MIN_KT, "gemm_tail_min_kt", 40)   \
-  X(OPT_GEMM_TAIL_V2, "gemm_tail_v2", 0)            \
   X(OPT_SPLITK_MIN_KT, "splitk_min_kt", 0)          \
   X(OPT_SPLITK_ROUNDS, "splitk_rounds", 1)          \
   X(OPT_GEMM_GROUP_M, "gemm_group_m", 0)            \

@@ -509,9 +509,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_v2(GemmArgs g, EpiParams e, 
 // ------------------------------------------------------------------------------------------------------------
 constexpr int HALF = 128 * BK;            // elements per half-tile image (16 KiB)
 
-// Epilogue specialisations of v4 (chosen on the host; every one computes exactly what epilogue4 computes for the
-// arguments it is chosen for).  Rows are written full-width from the LDS image, with per-column state (bias) loaded
-// once per tile instead of once per row.
+// Epilogue specialisations of v4 (chosen on the host by v4_kind; every one computes exactly what epilogue4 computes
+// for the arguments it is chosen for).  Rows are written full-width from the LDS image, with per-column state (bias)
+// loaded once per tile instead of once per row.
 enum EpiKind : int {
   EPI_PLAIN = 0,      // alpha * acc
   EPI_BIAS_ACT = 1,   // act(alpha * acc + bias)
@@ -525,42 +525,20 @@ enum EpiKind : int {
 };
 
 // Kinds whose row epilogue reads a second [m][n]-shaped bf16 operand (ReLU mask / residual).  Those reads are
-// issued for all 32 rows a wave owns BEFORE the accumulators go through LDS (raw bf16x4 per lane and row), so the
-// epilogue pays one memory latency per tile instead of one per group of rows — each dependent load also waited for
-// every store issued before it (one vmcnt counter).
+// issued for the rows of a 128-row half BEFORE their accumulators are processed, so the epilogue pays one memory
+// latency per half-tile instead of one per group of rows — each dependent load also waited for every store issued
+// before it (one vmcnt counter).
 template <int KIND>
 VIT_DEV bool v4_has_pre(const EpiParams& e) {
   return KIND == EPI_AUX || KIND == EPI_AUXM || (KIND == EPI_BDR && e.res != nullptr);
 }
 
-template <int KIND>
-VIT_DEV uint2 v4_pre_load(const EpiParams& e, int64_t i, int64_t j) {
-  uint2 r = make_uint2(0u, 0u);
-  if (KIND == EPI_AUXM) {                          // i % 4 == 0: the dword of rows i..i+3 (row groups are allocated whole)
-    if (i < e.m && j < e.n) r.x = *reinterpret_cast<const uint32_t*>((const uint8_t*)e.aux + mask4_byte(i, j, e.n));
-    return r;
-  }
-  if (i < e.m && j < e.n) {
-    const bf16_t* p = KIND == EPI_AUX ? (const bf16_t*)e.aux + i * e.ldaux + j : (const bf16_t*)e.res + i * e.ldres + j;
-    r = *reinterpret_cast<const uint2*>(p);
-  }
-  return r;
-}
-
-VIT_DEV void unpack_bf16x4(uint2 u, float (&a)[4]) {
-  a[0] = __uint_as_float(u.x << 16);
-  a[1] = __uint_as_float(u.x & 0xffff0000u);
-  a[2] = __uint_as_float(u.y << 16);
-  a[3] = __uint_as_float(u.y & 0xffff0000u);
-}
-
-// Returns the row's mask4 nibble (dropout keep bits for EPI_BDR with dropout, else stored value > 0) for the fast
-// kinds that produce one (the caller stores 4 rows' nibbles as one dword); 0 otherwise.
-// ACT (EPI_BIAS_ACT only): 0 none, 1 ReLU, 2 GELU(erf) — a template argument, so the row code carries no runtime
-// activation branches (the erf body was inlined four times behind them in every unrolled row).
-template <class TO, int KIND, int ACT>
+// One row piece of 4 columns of the LDS-image epilogue (v4_epilogue): the general epilogue, the split-K slab, or
+// gelu(alpha * acc + bias), for which it returns the row's mask4 nibble (stored value > 0; the caller stores 4 rows'
+// nibbles as one dword); 0 otherwise.
+template <class TO, int KIND>
 VIT_DEV uint32_t v4_epi_row(const EpiParams& e, const GemmArgs& g, int64_t i, int64_t j, const float (&b4)[4],
-                            float v[4], uint2 pre = make_uint2(0u, 0u)) {
+                            float v[4]) {
   if (KIND == EPI_GENERAL) {
     epilogue4<TO>(e, i, j, v);
     return 0u;
@@ -572,47 +550,11 @@ VIT_DEV uint32_t v4_epi_row(const EpiParams& e, const GemmArgs& g, int64_t i, in
   if (i >= e.m || j >= e.n) return 0u;              // fast kinds: n % 4 == 0 and 16-B aligned rows (e.vec)
 #pragma unroll
   for (int r = 0; r < 4; ++r) v[r] *= e.alpha;
-  if (KIND == EPI_BIAS_ACT || KIND == EPI_BDR) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] += b4[r];
-  }
-  if (KIND == EPI_BIAS_ACT && ACT == 1) {
+  for (int r = 0; r < 4; ++r) v[r] += b4[r];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-  } else if (KIND == EPI_BIAS_ACT && ACT == 2) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-  }
-  if (KIND == EPI_AUX) {                            // aux is bf16 (host-checked), prefetched
-    float a[4];
-    unpack_bf16x4(pre, a);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = a[r] > 0.f ? v[r] : 0.f;
-  }
-  if (KIND == EPI_AUXM) {                           // pre.x = this row's mask4 nibble
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = (pre.x >> r) & 1u ? v[r] : 0.f;
-  }
-  uint32_t keep = 0u;
-  if (KIND == EPI_BDR) {
-    if (e.use_drop) {
-      const uint32_t base = (uint32_t)((i + e.row0) * e.drop_rs * e.n + j);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const bool k = vit_hash_u32(e.seed, base + r) >= e.drop_thr;
-        keep |= (uint32_t)k << r;
-        v[r] = k ? v[r] * e.drop_scale : 0.f;
-      }
-    }
-    if (e.res) {                                     // res is bf16 (host-checked), prefetched
-      float a[4];
-      unpack_bf16x4(pre, a);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] += a[r];
-    }
-  }
+  for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
   st4<TO>((TO*)e.c + i * e.ldc + j, v);
-  if (KIND == EPI_BDR && e.use_drop) return keep;
   uint32_t pos = 0u;
 #pragma unroll
   for (int r = 0; r < 4; ++r) pos |= (uint32_t)(sizeof(TO) == 2 ? bf2f(f2bf(v[r])) > 0.f : v[r] > 0.f) << r;
@@ -721,38 +663,28 @@ VIT_DEV void mfma_quadrant(f32x4 (&acc)[4][2], const bf16x8_t (&af)[4][2], const
 // (8 rows per lane group) and reads (16 chunks of one row per group).  A pass's 16 row reads are issued together
 // before any row is processed: one row at a time (read, lgkmcnt(0), math, store) was a serial LDS-latency chain of
 // ~8 us per tile at two waves per SIMD.
+// The kinds that come here: the general epilogue, the split-K slab, and bias + GELU (erf x 8 per piece spills in the
+// direct wide epilogue); every other fast kind runs v4_epilogue_d.
 template <class TO, int KIND, int ACT>
 VIT_DEV void v4_epilogue(const EpiParams& e, const GemmArgs& g, const f32x4 (&acc)[2][2][4][2], bf16_t* smem4,
                          int tid, int64_t i0, int64_t j0, int64_t tm) {
+  static_assert(KIND == EPI_GENERAL || KIND == EPI_SLAB || (KIND == EPI_BIAS_ACT && ACT == 2),
+                "LDS-image epilogue: general, slab, or bias + GELU");
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
   float* ep = reinterpret_cast<float*>(smem4);
   const int64_t jcol = j0 + 4 * lane;
   float b4[4] = {0.f, 0.f, 0.f, 0.f};
-  if ((KIND == EPI_BIAS_ACT || KIND == EPI_BDR) && e.bias && jcol < e.n) ld4<float>(e.bias + jcol, b4);
-  // second-operand rows of both passes, in flight before the LDS round trip (see v4_has_pre)
-  uint2 pre[2][16];
-  const bool has_pre = v4_has_pre<KIND>(e);
+  if (KIND == EPI_BIAS_ACT && e.bias && jcol < e.n) ld4<float>(e.bias + jcol, b4);
   // fused column sums of C as stored (the bias gradient of the Linear whose input gradient C is)
-  const bool cs_on = (KIND == EPI_PLAIN || KIND == EPI_BIAS_ACT || KIND == EPI_AUX || KIND == EPI_AUXM ||
-                      KIND == EPI_BDR) && e.csum != nullptr;
+  const bool cs_on = KIND == EPI_BIAS_ACT && e.csum != nullptr;
   // mask4 of C: 4 rows' nibbles of this lane's column group -> one dword store per 4 rows (EPI_GENERAL writes it in
   // epilogue4, the split-K reduce after EPI_SLAB)
-  const bool mk_on = KIND != EPI_GENERAL && KIND != EPI_SLAB && e.mask_out != nullptr;
+  const bool mk_on = KIND == EPI_BIAS_ACT && e.mask_out != nullptr;
   uint32_t mword = 0u;
   float cs[4] = {0.f, 0.f, 0.f, 0.f};
-  if (has_pre) {
-#pragma unroll
-    for (int mh = 0; mh < 2; ++mh)
-#pragma unroll
-      for (int rr = 0; rr < 16; ++rr) {
-        if (KIND != EPI_AUXM) pre[mh][rr] = v4_pre_load<KIND>(e, i0 + mh * 128 + wave * 16 + rr, jcol);
-        else if ((rr & 3) == 0) pre[mh][rr] = v4_pre_load<KIND>(e, i0 + mh * 128 + wave * 16 + rr, jcol);
-        else pre[mh][rr] = make_uint2(pre[mh][rr & ~3].x >> (8 * (rr & 3)), 0u);
-      }
-  }
-  __syncthreads();                                        // every wave's k-loop LDS reads are done, no DMA pending
+  __syncthreads();                                      // every wave's k-loop LDS reads are done, no DMA pending
 #pragma unroll
   for (int mh = 0; mh < 2; ++mh) {
 #pragma unroll
@@ -777,7 +709,7 @@ VIT_DEV void v4_epilogue(const EpiParams& e, const GemmArgs& g, const f32x4 (&ac
       const int row = wave * 16 + rr;
       float v[4] = {rv[rr][0], rv[rr][1], rv[rr][2], rv[rr][3]};
       const int64_t i = i0 + mh * 128 + row, j = j0 + 4 * lane;
-      const uint32_t nib = v4_epi_row<TO, KIND, ACT>(e, g, i, j, b4, v, has_pre ? pre[mh][rr] : make_uint2(0u, 0u));
+      const uint32_t nib = v4_epi_row<TO, KIND>(e, g, i, j, b4, v);
       if (mk_on) {
         mword |= (nib & 0xfu) << (8 * (rr & 3));
         if ((rr & 3) == 3) {                            // rows i-3..i: one dword (row groups are allocated whole)
@@ -1224,10 +1156,12 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
     const int tid_e = remat(tid);
     if constexpr (WIDE) {
       float* csl = reinterpret_cast<float*>(smem4 + V4_SLOTS * HALF);
-      if (KIND == EPI_BIAS_ACT && e.act == VIT_ACT_RELU) v4_epilogue_dd<KIND, 1>(e, acc, csl, tid_e, i0, j0, tm);
-      else if (KIND == EPI_BIAS_ACT && e.act == VIT_ACT_GELU) {  // (the head only; erf x 8 per piece spills)
-        __syncthreads();
-        v4_epilogue<TO, KIND, 2>(e, g, acc, smem4, tid_e, i0, j0, tm);
+      if constexpr (KIND == EPI_BIAS_ACT) {
+        if (e.act == VIT_ACT_RELU) v4_epilogue_dd<KIND, 1>(e, acc, csl, tid_e, i0, j0, tm);
+        else if (e.act == VIT_ACT_GELU) {                        // (the head only; erf x 8 per piece spills)
+          __syncthreads();
+          v4_epilogue<TO, KIND, 2>(e, g, acc, smem4, tid_e, i0, j0, tm);
+        } else v4_epilogue_dd<KIND, 0>(e, acc, csl, tid_e, i0, j0, tm);
       } else v4_epilogue_dd<KIND, 0>(e, acc, csl, tid_e, i0, j0, tm);
     } else {
       GemmArgs gi = g;
@@ -1370,9 +1304,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 bool aligned(const void* p, int a) { return p == nullptr || (((uintptr_t)p) % a) == 0; }
 
+// Host side: gemm_validate (the caller's descriptor, once) -> gemm_run plans one launch (kernel generation by
+// gemm_impl, the v4 epilogue kind by v4_kind, grids) and launches it through launch_bf16's one switch (launch_f32 for
+// fp32 inputs) -> vit_gemm wraps that in the split-K tail (tail_split).
+//
 // bf16 kernels: 1 = register-staged 128x128, 2 = LDS-DMA 128x128, 4 = LDS-DMA 256x256 ping-pong.
 // Option "gemm_impl" forces a kernel (A/B runs and the per-variant tests); 0 = automatic: v4 when both output dims
-// span a 256 tile, else v2.
+// span a 256 tile, else v2.  gemm_run demotes 2 and 4 to 1 when the LDS-DMA kernels cannot take the operands.
 int gemm_impl_env() {
   const int64_t v = vit::opt(vit::OPT_GEMM_IMPL);
   return (v == 1 || v == 2 || v == 4) ? (int)v : 0;
@@ -1410,26 +1348,143 @@ int tail_split(const vit_gemm_desc* d, int64_t* m_main) {
   return (int)sk;
 }
 
-// Option gemm_tail_v2 (off by default): the rows of a last partial round of 256x256 tiles that the split-K tail does
-// not take (K below gemm_tail_min_kt k-tiles: proj and its input gradient, fc1, the fc2 input gradient at ViT-B/16
-// C2) run as 128x128 tiles (v2, two workgroups per CU): the 81 tiles of the third round of an N = 768 GEMM become 324
-// quarter-tiles that all run at once, instead of 81 whole tiles on a third of the CUs.  Measured (round 5, one box,
-// bench.py --opt gemm_tail_v2=0/1): 31.6 vs 33.0 ms/step — the v2 tiles with the general epilogue (and the separate
-// column-sum pass) cost more than the idle CUs of the whole-tile round.  Returns 1 and *m_main = the rows of the
-// whole rounds.
-int tail_rows_v2(const vit_gemm_desc* d, int64_t* m_main) {
-  *m_main = d->m;
-  if (!vit::opt(vit::OPT_GEMM_TAIL_V2)) return 0;
-  if (d->split_k > 1 || d->in_dtype != VIT_BF16 || d->k % BK != 0 || d->m <= 0 || d->n <= 0) return 0;
-  if (gemm_impl(d->m, d->n) != 4 || d->out_group_rows != 0 || d->res_rowmod != 0) return 0;
-  const int64_t tn = (d->n + 255) / 256, tm = (d->m + 255) / 256;
-  const int64_t rounds = tm * tn / 256;
-  if (rounds < 1) return 0;
-  const int64_t mr = rounds * 256 / tn;                    // tile rows that fill whole rounds
-  const int64_t tail = (tm - mr) * tn;
-  if (tail <= 0 || 2 * tail > 256) return 0;
-  *m_main = mr * 256;
-  return 1;
+// Everything vit_gemm requires of the caller's descriptor (what depends on a sub-launch — the split-K workspace, the
+// work-item count — is checked in gemm_run).  The row ranges of the split-K tail inherit all of it: they start at a
+// multiple of 256 rows.
+int gemm_validate(const vit_gemm_desc* d) {
+  VIT_REQUIRE(d != nullptr, "vit_gemm: null descriptor");
+  VIT_REQUIRE(d->a && d->b && d->c, "vit_gemm: null operand pointer");
+  VIT_REQUIRE(!d->colsum_part || d->out_group_rows == 0, "vit_gemm: colsum_part needs ungrouped output rows");
+  VIT_REQUIRE(d->m > 0 && d->n > 0 && d->k > 0, "vit_gemm: bad shape m=%lld n=%lld k=%lld", (long long)d->m,
+              (long long)d->n, (long long)d->k);
+  VIT_REQUIRE(d->in_dtype == VIT_F32 || d->in_dtype == VIT_BF16, "vit_gemm: bad in_dtype %d", d->in_dtype);
+  VIT_REQUIRE(d->out_dtype == VIT_F32 || d->out_dtype == VIT_BF16, "vit_gemm: bad out_dtype %d", d->out_dtype);
+  VIT_REQUIRE(d->beta == 0.f || d->out_dtype == VIT_F32, "vit_gemm: beta requires f32 output");
+  VIT_REQUIRE(!d->aux || d->aux_dtype == VIT_F32 || d->aux_dtype == VIT_BF16 || d->aux_dtype == VIT_MASK4,
+              "vit_gemm: bad aux_dtype %d", d->aux_dtype);
+  VIT_REQUIRE(!d->mask_out || d->out_group_rows == 0, "vit_gemm: mask_out needs ungrouped output rows");
+  VIT_REQUIRE(!d->mask_out || aligned(d->mask_out, 4), "vit_gemm: mask_out must be 4-B aligned");
+  VIT_REQUIRE(!d->aux || d->aux_dtype != VIT_MASK4 || aligned(d->aux, 4), "vit_gemm: mask4 aux must be 4-B aligned");
+  VIT_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "vit_gemm: dropout_p out of range");
+  if (d->in_dtype == VIT_BF16) {
+    const bool akc = d->a_kcontig != 0, bkc = d->b_kcontig != 0;
+    VIT_REQUIRE(aligned(d->a, 16) && aligned(d->b, 16), "vit_gemm(bf16): operands must be 16-B aligned");
+    VIT_REQUIRE(d->lda % 8 == 0 && d->ldb % 8 == 0, "vit_gemm(bf16): lda/ldb must be multiples of 8");
+    VIT_REQUIRE(akc ? d->k % 8 == 0 : d->m % 8 == 0, "vit_gemm(bf16): A contiguous dim must be a multiple of 8");
+    VIT_REQUIRE(bkc ? d->k % 8 == 0 : d->n % 8 == 0, "vit_gemm(bf16): B contiguous dim must be a multiple of 8");
+    VIT_REQUIRE(akc || !bkc, "vit_gemm(bf16): layout (A rowstrided, B kcontig) is not provided");
+  }
+  return VIT_OK;
+}
+
+// The epilogue's arguments from a descriptor; row0 = global row of local row 0 (dropout indices).  csum stays null:
+// the launcher sets it when the kernel fuses the column sums.
+EpiParams make_epi(const vit_gemm_desc* d, int64_t row0) {
+  EpiParams e{};
+  e.c = d->c; e.ldc = d->ldc; e.m = d->m; e.n = d->n;
+  e.alpha = d->alpha; e.beta = d->beta; e.bias = d->bias; e.act = d->act;
+  e.aux = d->aux; e.ldaux = d->ldaux; e.aux_dtype = d->aux_dtype;
+  e.res = d->res; e.ldres = d->ldres; e.res_rowmod = d->res_rowmod; e.res_dtype = d->res_dtype;
+  e.use_drop = d->dropout_p > 0.f;
+  e.drop_thr = e.use_drop ? vit_drop_threshold(d->dropout_p) : 0;
+  e.seed = d->dropout_seed;
+  e.drop_scale = e.use_drop ? 1.0f / (1.0f - d->dropout_p) : 1.0f;
+  e.grp = d->out_group_rows;
+  e.grp_stride = d->out_group_stride;
+  e.row0 = row0;
+  e.mask_out = (uint8_t*)d->mask_out;
+  e.drop_rs = d->dropout_row_stride > 1 ? d->dropout_row_stride : 1;
+  e.vec = (d->n % 4 == 0) && (d->ldc % 4 == 0) && aligned(d->c, 16) && aligned(d->bias, 16) &&
+          (!d->aux || d->aux_dtype == VIT_MASK4 || (d->ldaux % 4 == 0 && aligned(d->aux, 16))) &&
+          (!d->res || (d->ldres % 4 == 0 && aligned(d->res, 16)));
+  e.vec8 = e.vec && d->n % 8 == 0 && d->ldc % 8 == 0 &&
+           (!d->aux || d->aux_dtype == VIT_MASK4 || (d->ldaux % 8 == 0 && aligned(d->aux, 16))) &&
+           (!d->res || (d->ldres % 8 == 0 && aligned(d->res, 16))) && (!d->mask_out || aligned(d->mask_out, 8)) &&
+           (!d->aux || d->aux_dtype != VIT_MASK4 || aligned(d->aux, 8));
+  return e;
+}
+
+// Which fast v4 epilogue kind is used on which operand layout: the layouts the training step runs it on and the tests
+// cover (forward: both k-contiguous; ReLU backward: the input-gradient layout).  PLAIN is used on all three.
+constexpr bool kind_has(int kind, bool akc, bool bkc) {
+  switch (kind) {
+    case EPI_BIAS_ACT: case EPI_BDR: case EPI_PATCH: return akc && bkc;
+    case EPI_AUX: case EPI_AUXM: return akc && !bkc;
+    default: return true;
+  }
+}
+
+// The v4 epilogue kind that is launched: the slab for a K split; else the fast kind that computes exactly this
+// epilogue, when there is one, it exists for the layout, and its wide bf16 rows are possible (bf16 output, e.vec8);
+// else the general one (also on option gemm_epi_general: A/B runs and the tests' reference).
+int v4_kind(const EpiParams& e, bool akc, bool bkc, bool out_bf, int split) {
+  if (split > 1) return EPI_SLAB;
+  if (!out_bf || !e.vec8 || e.beta != 0.f || vit::opt(vit::OPT_GEMM_EPI_GENERAL)) return EPI_GENERAL;
+  const bool rows_plain = e.grp == 0 && e.res_rowmod == 0;     // C row i, residual row i
+  const bool lin = !e.aux && !e.use_drop && !e.res;            // nothing after bias / activation
+  const bool no_ba = !e.bias && e.act == VIT_ACT_NONE;
+  int kind = EPI_GENERAL;
+  if (rows_plain && lin && no_ba) kind = EPI_PLAIN;
+  else if (rows_plain && lin && e.bias) kind = EPI_BIAS_ACT;
+  else if (rows_plain && e.aux && no_ba && !e.use_drop && !e.res && e.aux_dtype != VIT_F32)
+    kind = e.aux_dtype == VIT_BF16 ? EPI_AUX : EPI_AUXM;
+  else if (rows_plain && !e.aux && e.act == VIT_ACT_NONE && (e.use_drop || e.res) &&
+           (!e.res || e.res_dtype == VIT_BF16))
+    kind = EPI_BDR;
+  else if (e.grp > 0 && e.res_rowmod > 0 && e.bias && e.res && e.res_dtype == VIT_F32 && e.act == VIT_ACT_NONE &&
+           !e.aux && !e.use_drop && e.m < 0x7fffffffLL)
+    kind = EPI_PATCH;
+  return kind_has(kind, akc, bkc) ? kind : EPI_GENERAL;
+}
+
+// One bf16 / f32 launch: what every kernel variant takes
+struct Launch {
+  GemmArgs g;
+  EpiParams e;
+  int64_t a_bytes, b_bytes;   // operand extents (the v2 kernel's buffer range check)
+  dim3 grid;
+  hipStream_t s;
+};
+
+template <bool AKC, bool BKC, class TO, int KIND>
+void launch_v4(const Launch& L) {
+  gemm_bf16_v4<AKC, BKC, TO, KIND><<<L.grid, 512, 0, L.s>>>(L.g, L.e, L.a_bytes, L.b_bytes);
+}
+
+// The bf16 kernel of one operand layout: impl = the kernel generation (gemm_impl), kind = v4_kind's (impl 4),
+// to_bf = the kernel stores bf16.  Every bf16 kind is instantiated for every layout, also where kind_has never
+// chooses it: without those instantiations the compiler emits different code for the kinds that do run.
+template <bool AKC, bool BKC>
+void launch_bf16(int impl, int kind, bool to_bf, const Launch& L) {
+  if (impl == 4) {
+    if (!to_bf) {
+      if (kind == EPI_SLAB) launch_v4<AKC, BKC, float, EPI_SLAB>(L);
+      else launch_v4<AKC, BKC, float, EPI_GENERAL>(L);
+      return;
+    }
+    switch (kind) {
+      case EPI_PLAIN: return launch_v4<AKC, BKC, bf16_t, EPI_PLAIN>(L);
+      case EPI_BIAS_ACT: return launch_v4<AKC, BKC, bf16_t, EPI_BIAS_ACT>(L);
+      case EPI_BDR: return launch_v4<AKC, BKC, bf16_t, EPI_BDR>(L);
+      case EPI_AUX: return launch_v4<AKC, BKC, bf16_t, EPI_AUX>(L);
+      case EPI_AUXM: return launch_v4<AKC, BKC, bf16_t, EPI_AUXM>(L);
+      case EPI_PATCH: return launch_v4<AKC, BKC, bf16_t, EPI_PATCH>(L);
+      default: return launch_v4<AKC, BKC, bf16_t, EPI_GENERAL>(L);
+    }
+  }
+  if (impl == 2) {
+    if (to_bf) gemm_bf16_v2<AKC, BKC, bf16_t><<<L.grid, 256, 0, L.s>>>(L.g, L.e, L.a_bytes, L.b_bytes);
+    else gemm_bf16_v2<AKC, BKC, float><<<L.grid, 256, 0, L.s>>>(L.g, L.e, L.a_bytes, L.b_bytes);
+  } else {
+    if (to_bf) gemm_bf16_kernel<AKC, BKC, bf16_t><<<L.grid, 256, 0, L.s>>>(L.g, L.e);
+    else gemm_bf16_kernel<AKC, BKC, float><<<L.grid, 256, 0, L.s>>>(L.g, L.e);
+  }
+}
+
+template <bool AKC, bool BKC>
+void launch_f32(bool to_bf, const Launch& L) {
+  if (to_bf) gemm_f32_kernel<AKC, BKC, bf16_t><<<L.grid, 256, 0, L.s>>>(L.g, L.e);
+  else gemm_f32_kernel<AKC, BKC, float><<<L.grid, 256, 0, L.s>>>(L.g, L.e);
 }
 
 }  // namespace
@@ -1463,219 +1518,111 @@ extern "C" int vit_gemm_split_k_hint(int64_t m, int64_t n, int64_t k, int in_dty
   return (int)std::max<int64_t>(1, s);
 }
 
-// One GEMM launch (+ the split-K reduce, + the column-sum pass when it is not fused); row0 = global row of local
-// row 0 (dropout indices).
-static int gemm_run(const vit_gemm_desc* d, int64_t row0, void* stream, int force_impl = 0) {
-  VIT_REQUIRE(d != nullptr, "vit_gemm: null descriptor");
-  VIT_REQUIRE(d->a && d->b && d->c, "vit_gemm: null operand pointer");
-  VIT_REQUIRE(!d->colsum_part || d->out_group_rows == 0, "vit_gemm: colsum_part needs ungrouped output rows");
-  VIT_REQUIRE(d->m > 0 && d->n > 0 && d->k > 0, "vit_gemm: bad shape m=%lld n=%lld k=%lld", (long long)d->m,
-              (long long)d->n, (long long)d->k);
-  VIT_REQUIRE(d->in_dtype == VIT_F32 || d->in_dtype == VIT_BF16, "vit_gemm: bad in_dtype %d", d->in_dtype);
-  VIT_REQUIRE(d->out_dtype == VIT_F32 || d->out_dtype == VIT_BF16, "vit_gemm: bad out_dtype %d", d->out_dtype);
-  VIT_REQUIRE(d->beta == 0.f || d->out_dtype == VIT_F32, "vit_gemm: beta requires f32 output");
-  VIT_REQUIRE(!d->aux || d->aux_dtype == VIT_F32 || d->aux_dtype == VIT_BF16 || d->aux_dtype == VIT_MASK4,
-              "vit_gemm: bad aux_dtype %d", d->aux_dtype);
-  VIT_REQUIRE(!d->mask_out || d->out_group_rows == 0, "vit_gemm: mask_out needs ungrouped output rows");
-  VIT_REQUIRE(!d->mask_out || aligned(d->mask_out, 4), "vit_gemm: mask_out must be 4-B aligned");
-  VIT_REQUIRE(!d->aux || d->aux_dtype != VIT_MASK4 || aligned(d->aux, 4), "vit_gemm: mask4 aux must be 4-B aligned");
-  VIT_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "vit_gemm: dropout_p out of range");
+
+// One GEMM launch of a validated descriptor (+ the split-K reduce, + the column-sum pass when it is not fused);
+// row0 = global row of local row 0 (dropout indices).
+static int gemm_run(const vit_gemm_desc* d, int64_t row0, void* stream) {
   const int split = d->split_k > 1 ? d->split_k : 1;
-
-  EpiParams e{};
-  e.c = d->c; e.ldc = d->ldc; e.m = d->m; e.n = d->n;
-  e.alpha = d->alpha; e.beta = d->beta; e.bias = d->bias; e.act = d->act;
-  e.aux = d->aux; e.ldaux = d->ldaux; e.aux_dtype = d->aux_dtype;
-  e.res = d->res; e.ldres = d->ldres; e.res_rowmod = d->res_rowmod; e.res_dtype = d->res_dtype;
-  e.use_drop = d->dropout_p > 0.f;
-  e.drop_thr = 0;
-  if (e.use_drop) {
-    double t = (double)d->dropout_p * 4294967296.0;
-    e.drop_thr = t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
-  }
-  e.seed = d->dropout_seed;
-  e.drop_scale = e.use_drop ? 1.0f / (1.0f - d->dropout_p) : 1.0f;
-  e.grp = d->out_group_rows;
-  e.grp_stride = d->out_group_stride;
-  e.csum = nullptr;
-  e.row0 = row0;
-  e.mask_out = (uint8_t*)d->mask_out;
-  e.drop_rs = d->dropout_row_stride > 1 ? d->dropout_row_stride : 1;
-  bool cs_fused = false;
-  e.vec = (d->n % 4 == 0) && (d->ldc % 4 == 0) && aligned(d->c, 16) && aligned(d->bias, 16) &&
-          (!d->aux || d->aux_dtype == VIT_MASK4 || (d->ldaux % 4 == 0 && aligned(d->aux, 16))) &&
-          (!d->res || (d->ldres % 4 == 0 && aligned(d->res, 16)));
-  e.vec8 = e.vec && d->n % 8 == 0 && d->ldc % 8 == 0 &&
-           (!d->aux || d->aux_dtype == VIT_MASK4 || (d->ldaux % 8 == 0 && aligned(d->aux, 16))) &&
-           (!d->res || (d->ldres % 8 == 0 && aligned(d->res, 16))) && (!d->mask_out || aligned(d->mask_out, 8)) &&
-           (!d->aux || d->aux_dtype != VIT_MASK4 || aligned(d->aux, 8));
-
-  GemmArgs g{};
+  const bool in_bf = d->in_dtype == VIT_BF16, out_bf = d->out_dtype == VIT_BF16;
+  const bool to_bf = out_bf && split == 1;              // the GEMM kernel stores C itself (else fp32 slabs / fp32 C)
+  const bool akc = d->a_kcontig != 0, bkc = d->b_kcontig != 0;
+  Launch L{};
+  L.e = make_epi(d, row0);
+  L.s = VIT_STREAM(stream);
+  GemmArgs& g = L.g;
   g.a = d->a; g.b = d->b; g.lda = d->lda; g.ldb = d->ldb; g.M = d->m; g.N = d->n; g.K = d->k;
-  g.ws = nullptr;
   if (split > 1) {
     VIT_REQUIRE(d->workspace && d->workspace_bytes >= vit_gemm_workspace_bytes(d),
                 "vit_gemm: split_k=%d needs %lld workspace bytes", split, (long long)vit_gemm_workspace_bytes(d));
     g.ws = (float*)d->workspace;
   }
-  hipStream_t s = VIT_STREAM(stream);
-  const bool out_bf = d->out_dtype == VIT_BF16;
 
-  if (d->in_dtype == VIT_BF16) {
-    const bool akc = d->a_kcontig != 0, bkc = d->b_kcontig != 0;
-    VIT_REQUIRE(aligned(d->a, 16) && aligned(d->b, 16), "vit_gemm(bf16): operands must be 16-B aligned");
-    VIT_REQUIRE(d->lda % 8 == 0 && d->ldb % 8 == 0, "vit_gemm(bf16): lda/ldb must be multiples of 8");
-    VIT_REQUIRE(akc ? d->k % 8 == 0 : d->m % 8 == 0, "vit_gemm(bf16): A contiguous dim must be a multiple of 8");
-    VIT_REQUIRE(bkc ? d->k % 8 == 0 : d->n % 8 == 0, "vit_gemm(bf16): B contiguous dim must be a multiple of 8");
-    VIT_REQUIRE(akc || !bkc, "vit_gemm(bf16): layout (A rowstrided, B kcontig) is not provided");
-    g.tiles_n = (d->n + BN - 1) / BN;
-    const int64_t tiles = ((d->m + BM - 1) / BM) * g.tiles_n;
-    const int64_t nkt = (d->k + BK - 1) / BK;
-    g.kt_per_split = (nkt + split - 1) / split;
-    dim3 grid((unsigned)tiles, (unsigned)split), block(256);
-    // operand extents in bytes (for the buffer-descriptor range check of the v2 kernel)
-    const int64_t a_bytes = (akc ? (d->m - 1) * d->lda + d->k : (d->k - 1) * d->lda + d->m) * 2;
-    const int64_t b_bytes = (bkc ? (d->n - 1) * d->ldb + d->k : (d->k - 1) * d->ldb + d->n) * 2;
-    // v2/v4 (LDS-DMA) need whole 64-deep k-tiles (split boundaries are k-tile aligned) and operands < 2 GiB
-    const int impl = force_impl ? force_impl : gemm_impl(d->m, d->n);
-    const bool dma_ok = d->k % BK == 0 && a_bytes < 0x7fffffffLL && b_bytes < 0x7fffffffLL;
-    const bool v2 = impl == 2 && dma_ok;
-    const bool v4 = impl == 4 && dma_ok;
-    GemmArgs g4 = g;
-    g4.tiles_n = (d->n + 255) / 256;
-    g4.tiles_m = (d->m + 255) / 256;
-    {
-      // Tile order inside an XCD's contiguous range: with many tile columns, row-major order puts ONE A panel and ~32
-      // B panels on an XCD at once (little L2 reuse); groups of 8 tile rows, column-major inside a group, give ~8 x 4.
-      // Measured (tools/gemm_ab.py): 8192^3 1146 -> 1566 TF/s; neutral on the ViT shapes (<= 12 tile columns).
-      const int64_t gopt = vit::opt(vit::OPT_GEMM_GROUP_M);
-      g4.group_m = gopt > 0 ? gopt : (g4.tiles_n >= 16 ? 8 : 1);
-      if (g4.group_m < 1) g4.group_m = 1;
-    }
-    g4.kt_per_split = (nkt + split - 1) / split;
-    g4.nitems = ((d->m + 255) / 256) * g4.tiles_n * split;     // tiles x K-slices, split-major
-    VIT_REQUIRE(g4.nitems < (1LL << 31), "vit_gemm: %lld tiles exceed the 2^31 work items of one launch",
-                (long long)g4.nitems);
-    dim3 grid4((unsigned)g4.nitems, 1u);
-    // v4 epilogue kind
-    const bool fast = e.vec && e.grp == 0 && e.res_rowmod == 0 && e.beta == 0.f;
-    int kind = EPI_GENERAL;
-    if (split > 1) kind = EPI_SLAB;
-    else if (fast && !e.bias && e.act == VIT_ACT_NONE && !e.aux && !e.use_drop && !e.res) kind = EPI_PLAIN;
-    else if (fast && e.bias && !e.aux && !e.use_drop && !e.res) kind = EPI_BIAS_ACT;
-    else if (fast && e.aux && e.aux_dtype == VIT_BF16 && !e.bias && e.act == VIT_ACT_NONE && !e.use_drop && !e.res)
-      kind = EPI_AUX;
-    else if (fast && e.aux && e.aux_dtype == VIT_MASK4 && !e.bias && e.act == VIT_ACT_NONE && !e.use_drop && !e.res)
-      kind = EPI_AUXM;
-    else if (fast && !e.aux && e.act == VIT_ACT_NONE && (e.use_drop || e.res) && (!e.res || e.res_dtype == VIT_BF16))
-      kind = EPI_BDR;
-    else if (e.vec && e.beta == 0.f && e.grp > 0 && e.res_rowmod > 0 && e.bias && e.res && e.res_dtype == VIT_F32 &&
-             e.act == VIT_ACT_NONE && !e.aux && !e.use_drop && d->m < 0x7fffffffLL && d->ldres % 8 == 0 &&
-             aligned(d->res, 16))
-      kind = EPI_PATCH;
-    if (vit::opt(vit::OPT_GEMM_EPI_GENERAL) && kind != EPI_SLAB) kind = EPI_GENERAL;   // A/B: the general epilogue
-    // the v4 epilogue instantiation that runs (fast kinds exist for bf16 output and these operand layouts only)
-    int launched = EPI_GENERAL;
-    if (kind == EPI_SLAB) launched = EPI_SLAB;
-    else if (out_bf && kind == EPI_PLAIN) launched = EPI_PLAIN;
-    else if (out_bf && akc && bkc && (kind == EPI_BIAS_ACT || kind == EPI_BDR)) launched = kind;
-    else if (out_bf && akc && !bkc && kind == EPI_AUX) launched = EPI_AUX;
-    else if (out_bf && akc && !bkc && kind == EPI_AUXM) launched = EPI_AUXM;
-    else if (out_bf && akc && bkc && kind == EPI_PATCH) launched = EPI_PATCH;
-    if (launched != EPI_SLAB && launched != EPI_GENERAL && !e.vec8) launched = EPI_GENERAL;  // wide epilogue needs 8-wide rows
-    cs_fused = v4 && d->colsum_part && launched != EPI_SLAB && launched != EPI_GENERAL;
-    // persistent grid (one workgroup per CU looping over items) for the wide-epilogue kinds; option gemm_persist 0:
-    // one workgroup per item (A/B switch)
-    {
-      const bool persist = launched != EPI_SLAB && launched != EPI_GENERAL && e.act != VIT_ACT_GELU &&
-                           !(d->flags & VIT_FLAG_SHARED_CUS) && vit::opt(vit::OPT_GEMM_PERSIST);
-      if (persist && g4.nitems > vit_cu_count()) grid4.x = (unsigned)vit_cu_count();
-    }
-    e.csum = cs_fused ? d->colsum_part : nullptr;
-#define V4(AK, BKK, TO, KIND) gemm_bf16_v4<AK, BKK, TO, KIND><<<grid4, 512, 0, s>>>(g4, e, a_bytes, b_bytes)
-#define LAUNCH_BF(AK, BKK)                                                                                     \
-  do {                                                                                                         \
-    if (v4) {                                                                                                  \
-      if (launched == EPI_SLAB) V4(AK, BKK, float, EPI_SLAB);                                                  \
-      else if (!out_bf) V4(AK, BKK, float, EPI_GENERAL);                                                       \
-      else if (launched == EPI_PLAIN) V4(AK, BKK, bf16_t, EPI_PLAIN);                                          \
-      else if (AK && BKK && launched == EPI_BIAS_ACT) V4(AK, BKK, bf16_t, EPI_BIAS_ACT);                       \
-      else if (AK && BKK && launched == EPI_BDR) V4(AK, BKK, bf16_t, EPI_BDR);                                 \
-      else if (AK && !BKK && launched == EPI_AUX) V4(AK, BKK, bf16_t, EPI_AUX);                                \
-      else if (AK && !BKK && launched == EPI_AUXM) V4(AK, BKK, bf16_t, EPI_AUXM);                              \
-      else if (AK && BKK && launched == EPI_PATCH) V4(AK, BKK, bf16_t, EPI_PATCH);                             \
-      else V4(AK, BKK, bf16_t, EPI_GENERAL);                                                                   \
-    } else if (v2) {                                                                                           \
-      if (out_bf && split == 1) gemm_bf16_v2<AK, BKK, bf16_t><<<grid, block, 0, s>>>(g, e, a_bytes, b_bytes);     \
-      else gemm_bf16_v2<AK, BKK, float><<<grid, block, 0, s>>>(g, e, a_bytes, b_bytes);                         \
-    } else {                                                                                                   \
-      if (out_bf && split == 1) gemm_bf16_kernel<AK, BKK, bf16_t><<<grid, block, 0, s>>>(g, e);                \
-      else gemm_bf16_kernel<AK, BKK, float><<<grid, block, 0, s>>>(g, e);                                      \
-    }                                                                                                          \
-  } while (0)
-    if (akc && bkc) LAUNCH_BF(true, true);
-    else if (akc && !bkc) LAUNCH_BF(true, false);
-    else LAUNCH_BF(false, false);
-#undef LAUNCH_BF
-#undef V4
+  // plan: kernel generation, tile, epilogue kind, grid
+  int impl = 0, kind = EPI_GENERAL;                     // impl 0: the f32 kernel
+  int64_t tile = FBM, bk = FBK;
+  if (in_bf) {
+    // operand extents in bytes; v2/v4 (LDS-DMA) need whole 64-deep k-tiles (split boundaries are k-tile aligned) and
+    // operands < 2 GiB
+    L.a_bytes = (akc ? (d->m - 1) * d->lda + d->k : (d->k - 1) * d->lda + d->m) * 2;
+    L.b_bytes = (bkc ? (d->n - 1) * d->ldb + d->k : (d->k - 1) * d->ldb + d->n) * 2;
+    const bool dma_ok = d->k % BK == 0 && L.a_bytes < 0x7fffffffLL && L.b_bytes < 0x7fffffffLL;
+    impl = dma_ok ? gemm_impl(d->m, d->n) : 1;
+    tile = impl == 4 ? 256 : BM;
+    bk = BK;
+    g.nitems = ((d->m + 255) / 256) * ((d->n + 255) / 256) * split;   // v4: tiles x K-slices, split-major
+    VIT_REQUIRE(g.nitems < (1LL << 31), "vit_gemm: %lld tiles exceed the 2^31 work items of one launch",
+                (long long)g.nitems);
+  }
+  g.tiles_m = (d->m + tile - 1) / tile;
+  g.tiles_n = (d->n + tile - 1) / tile;
+  g.kt_per_split = ((d->k + bk - 1) / bk + split - 1) / split;
+  L.grid = dim3((unsigned)(g.tiles_m * g.tiles_n), (unsigned)split);
+  bool cs_fused = false;
+  if (impl == 4) {
+    kind = v4_kind(L.e, akc, bkc, out_bf, split);
+    const bool wide = kind != EPI_SLAB && kind != EPI_GENERAL;   // bf16 rows straight from the accumulators
+    cs_fused = wide && d->colsum_part;
+    if (cs_fused) L.e.csum = d->colsum_part;
+    // Tile order inside an XCD's contiguous range: with many tile columns, row-major order puts ONE A panel and ~32
+    // B panels on an XCD at once (little L2 reuse); groups of 8 tile rows, column-major inside a group, give ~8 x 4.
+    // Measured (tools/gemm_ab.py): 8192^3 1146 -> 1566 TF/s; neutral on the ViT shapes (<= 12 tile columns).
+    const int64_t gopt = vit::opt(vit::OPT_GEMM_GROUP_M);
+    g.group_m = gopt > 0 ? gopt : (g.tiles_n >= 16 ? 8 : 1);
+    // persistent grid (one workgroup per CU looping over items) for the wide-epilogue kinds, except bias + GELU (the
+    // LDS-image epilogue); option gemm_persist 0: one workgroup per item (A/B switch)
+    const bool persist = wide && L.e.act != VIT_ACT_GELU && !(d->flags & VIT_FLAG_SHARED_CUS) &&
+                         vit::opt(vit::OPT_GEMM_PERSIST);
+    L.grid = dim3((unsigned)(persist ? std::min<int64_t>(g.nitems, vit_cu_count()) : g.nitems), 1u);
+  }
+
+  if (in_bf) {                                          // (A row-strided, B k-contiguous) is refused by gemm_validate
+    if (akc && bkc) launch_bf16<true, true>(impl, kind, to_bf, L);
+    else if (akc) launch_bf16<true, false>(impl, kind, to_bf, L);
+    else launch_bf16<false, false>(impl, kind, to_bf, L);
+  } else if (akc) {
+    if (bkc) launch_f32<true, true>(to_bf, L);
+    else launch_f32<true, false>(to_bf, L);
   } else {
-    g.tiles_n = (d->n + FBM - 1) / FBM;
-    const int64_t tiles = ((d->m + FBM - 1) / FBM) * g.tiles_n;
-    const int64_t nkt = (d->k + FBK - 1) / FBK;
-    g.kt_per_split = (nkt + split - 1) / split;
-    dim3 grid((unsigned)tiles, (unsigned)split), block(256);
-    const bool akc = d->a_kcontig != 0, bkc = d->b_kcontig != 0;
-#define LAUNCH_F(AK, BKK)                                                                               \
-  do {                                                                                                  \
-    if (out_bf && split == 1) gemm_f32_kernel<AK, BKK, bf16_t><<<grid, block, 0, s>>>(g, e);            \
-    else gemm_f32_kernel<AK, BKK, float><<<grid, block, 0, s>>>(g, e);                                  \
-  } while (0)
-    if (akc && bkc) LAUNCH_F(true, true);
-    else if (akc) LAUNCH_F(true, false);
-    else if (bkc) LAUNCH_F(false, true);
-    else LAUNCH_F(false, false);
-#undef LAUNCH_F
+    if (bkc) launch_f32<false, true>(to_bf, L);
+    else launch_f32<false, false>(to_bf, L);
   }
   if (split > 1) {
     const int64_t total = d->m * ((d->n + 3) / 4);
     const int64_t blocks = std::min<int64_t>((total + 255) / 256, 4096);
-    if (out_bf) splitk_reduce_kernel<bf16_t><<<(unsigned)blocks, 256, 0, s>>>(g.ws, d->m, d->n, split, e);
-    else splitk_reduce_kernel<float><<<(unsigned)blocks, 256, 0, s>>>(g.ws, d->m, d->n, split, e);
+    if (out_bf) splitk_reduce_kernel<bf16_t><<<(unsigned)blocks, 256, 0, L.s>>>(g.ws, d->m, d->n, split, L.e);
+    else splitk_reduce_kernel<float><<<(unsigned)blocks, 256, 0, L.s>>>(g.ws, d->m, d->n, split, L.e);
   }
   if (d->colsum_part && !cs_fused)
-    vit::colsum_parts_launch(d->c, d->ldc, d->out_dtype, d->m, d->n, 256, d->colsum_part, s);
+    vit::colsum_parts_launch(d->c, d->ldc, d->out_dtype, d->m, d->n, 256, d->colsum_part, L.s);
   return vit::check_launch("vit_gemm");
 }
 
+// The descriptor is validated once (gemm_validate); each launch is then planned and issued by gemm_run, whose kernel
+// and epilogue choices are gemm_impl's and v4_kind's alone.
 // When the 256x256 tiles leave the last round of the 256 CUs at most half full (tail_split), the whole rounds run as
 // one launch and the remaining tile rows run split-K over the otherwise idle CUs: fp32 slabs in the caller's
 // workspace, then the deterministic reduce applies the same epilogue (dropout indices keep the global row; column
 // sums land in the same colsum_part rows).  Without a large enough workspace the GEMM runs unsplit.
 extern "C" int vit_gemm(const vit_gemm_desc* d, void* stream) {
-  VIT_REQUIRE(d != nullptr, "vit_gemm: null descriptor");
+  if (const int rc = gemm_validate(d)) return rc;
   int64_t m_main = 0;
-  int sk = tail_split(d, &m_main);
-  const bool split_tail = sk > 1 && d->workspace && d->workspace_bytes >= vit_gemm_workspace_bytes(d);
-  const bool v2_tail = !split_tail && tail_rows_v2(d, &m_main);
-  if (split_tail || v2_tail) {
-    vit_gemm_desc dm = *d;
-    dm.m = m_main;
-    const int rc = gemm_run(&dm, d->dropout_row0, stream);
-    if (rc) return rc;
-    auto esz = [](int32_t t) { return t == VIT_BF16 ? (int64_t)2 : (int64_t)4; };
-    const int64_t r = m_main;
-    vit_gemm_desc dt = *d;
-    dt.a = (const char*)d->a + (d->a_kcontig ? r * d->lda : r) * 2;
-    dt.c = (char*)d->c + r * d->ldc * esz(d->out_dtype);
-    const int64_t mask_off = (r / 4) * ((d->n + 3) / 4) * 4;   // r % 256 == 0: whole mask4 row groups
-    if (d->aux) dt.aux = (const char*)d->aux + (d->aux_dtype == VIT_MASK4 ? mask_off : r * d->ldaux * esz(d->aux_dtype));
-    if (d->mask_out) dt.mask_out = (char*)d->mask_out + mask_off;
-    if (d->res) dt.res = (const char*)d->res + r * d->ldres * esz(d->res_dtype);
-    if (d->colsum_part) dt.colsum_part = d->colsum_part + (r / 256) * d->n;
-    dt.m = d->m - r;
-    if (v2_tail) return gemm_run(&dt, d->dropout_row0 + r, stream, 2);
-    dt.split_k = sk;
-    return gemm_run(&dt, d->dropout_row0 + r, stream);
-  }
-  return gemm_run(d, d->dropout_row0, stream);
+  const int sk = tail_split(d, &m_main);
+  if (sk <= 1 || !d->workspace || d->workspace_bytes < vit_gemm_workspace_bytes(d))
+    return gemm_run(d, d->dropout_row0, stream);
+  vit_gemm_desc dm = *d;
+  dm.m = m_main;
+  if (const int rc = gemm_run(&dm, d->dropout_row0, stream)) return rc;
+  auto esz = [](int32_t t) { return t == VIT_BF16 ? (int64_t)2 : (int64_t)4; };
+  const int64_t r = m_main;
+  vit_gemm_desc dt = *d;
+  dt.a = (const char*)d->a + (d->a_kcontig ? r * d->lda : r) * 2;
+  dt.c = (char*)d->c + r * d->ldc * esz(d->out_dtype);
+  const int64_t mask_off = (r / 4) * ((d->n + 3) / 4) * 4;   // r % 256 == 0: whole mask4 row groups
+  if (d->aux) dt.aux = (const char*)d->aux + (d->aux_dtype == VIT_MASK4 ? mask_off : r * d->ldaux * esz(d->aux_dtype));
+  if (d->mask_out) dt.mask_out = (char*)d->mask_out + mask_off;
+  if (d->res) dt.res = (const char*)d->res + r * d->ldres * esz(d->res_dtype);
+  if (d->colsum_part) dt.colsum_part = d->colsum_part + (r / 256) * d->n;
+  dt.m = d->m - r;
+  dt.split_k = sk;
+  return gemm_run(&dt, d->dropout_row0 + r, stream);
 }

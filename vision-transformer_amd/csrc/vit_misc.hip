@@ -524,8 +524,7 @@ extern "C" int vit_copy2d(const void* src, int64_t lds, int32_t src_dtype, void*
 extern "C" int vit_dropout_bwd(const void* x, void* y, int32_t dtype, int64_t n, float p, uint32_t seed, float scale,
                                void* stream) {
   VIT_REQUIRE(x && y && n > 0 && p >= 0.f && p < 1.f, "vit_dropout_bwd: bad arguments");
-  double t = (double)p * 4294967296.0;
-  const uint32_t thr = t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
+  const uint32_t thr = vit_drop_threshold(p);
   const unsigned grid = grid_for(n, 256, 16384);
   hipStream_t s = VIT_STREAM(stream);
   if (dtype == VIT_BF16) dropout_bwd_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, (bf16_t*)y, n, thr, scale, seed);

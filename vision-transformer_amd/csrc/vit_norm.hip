@@ -491,8 +491,7 @@ extern "C" int vit_layernorm_bwd(const void* dy, int64_t lddy, const void* x, in
   VIT_REQUIRE(cols <= 4096, "vit_layernorm_bwd: cols=%lld > 4096", (long long)cols);
   VIT_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "vit_layernorm_bwd: drop_p out of range");
   const int64_t parts = vit_layernorm_bwd_parts(rows, cols);
-  double t = (double)drop_p * 4294967296.0;
-  const uint32_t thr = t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
+  const uint32_t thr = vit_drop_threshold(drop_p);
   const float scale = 1.0f / (1.0f - drop_p);
   hipStream_t s = VIT_STREAM(stream);
   // bf16 rows up to 3072 columns: per-wave accumulators in LDS (13 KiB x NV per block); option ln_al 0: registers
