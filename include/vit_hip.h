@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VIT_ABI_VERSION 16
+#define VIT_ABI_VERSION 17
 
 typedef enum { VIT_OK = 0, VIT_ERR_INVALID = 1, VIT_ERR_LAUNCH = 2 } vit_status;
 typedef enum { VIT_F32 = 0, VIT_BF16 = 1, VIT_MASK4 = 2 } vit_dtype;
@@ -70,6 +70,8 @@ const char* vit_last_error(void);
  * that selected it: vit_set_option refuses that name.
  * ABI 16 removed the 128x128-tile second launch for a last partial round of 256x256 tiles, which measured slower (33.0
  * vs 31.6 ms/step), and its option name "gemm_tail_v2": refused likewise.
+ * ABI 17 adds the gradient-clipping entry points (vit_grad_sumsq, vit_grad_clip_finish, vit_adamw_clipped) and no
+ * option name: clipping is an argument of the optimizer, not a kernel variant.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -294,6 +296,33 @@ int vit_adamw(const vit_tensor_chunk* table_dev, int64_t nchunks, float lr, floa
               float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, int32_t shadow_dtype,
               void* stream);
 int vit_pack(const vit_tensor_chunk* table_dev, int64_t nchunks, int32_t shadow_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Gradient clipping by global norm, fused into the AdamW step (ABI 17).  The reference has no counterpart: its loop
+ * goes from loss.backward() straight to optimizer.step() (train.py:94-96); the formulas are those of
+ * torch.nn.utils.clip_grad_norm_.  Three launches on one stream, no host sync, no atomics; all sums are fp64 in a
+ * fixed order, so the results are bitwise reproducible.
+ *   vit_grad_sumsq:       partial[i] = sum over chunk i of (gs * g[t])^2   (gs = grad_scale, the product in fp32 as the
+ *                         update forms it, squared and summed in fp64); reads only the `g` and `n` fields of the table.
+ *                         Several tables may fill consecutive slices of one `partial` buffer.
+ *   vit_grad_clip_finish: one workgroup.  sum = partial[0] + ... + partial[nparts-1] in fp64, then clip[4] (fp32):
+ *                           clip[0] = norm = (float)sqrt(sum)
+ *                           clip[1] = coef = min(1, |max_norm| / (norm + 1e-6f))
+ *                           clip[2] = skip = 1 when max_norm > 0 and norm is inf or NaN, else 0; skip sets coef = 0
+ *                           clip[3] += skip   (running count of skipped steps; the caller zeroes it once)
+ *                         max_norm < 0 bounds the norm by |max_norm| and never skips: a non-finite norm then gives
+ *                         torch's coefficient (0 for inf, NaN for NaN), which reaches the update.  max_norm = 0 or NaN
+ *                         is refused.
+ *   vit_adamw_clipped:    vit_adamw with gs replaced by gs * clip[1]; when clip[2] != 0 it touches none of p, m, v or
+ *                         the shadows.  vit_adamw itself is unchanged.
+ * ------------------------------------------------------------------------------------------------------------ */
+int vit_grad_sumsq(const vit_tensor_chunk* table_dev, int64_t nchunks, float grad_scale,
+                   double* partial /* [nchunks] */, void* stream);
+int vit_grad_clip_finish(const double* partial, int64_t nparts, float max_norm,
+                         float* clip /* [4]: norm, coef, skip, skipped total */, void* stream);
+int vit_adamw_clipped(const vit_tensor_chunk* table_dev, int64_t nchunks, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
+                      int32_t shadow_dtype, const float* clip, void* stream);
 
 #ifdef __cplusplus
 }

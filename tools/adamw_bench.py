@@ -1,5 +1,10 @@
 """Time vit_adamw on the ViT-B/16 parameter set (C2: 562 tensors, 86.6M fp32 elements + bf16 shadows) for several
-multi-tensor chunk sizes (elements per workgroup).  usage: python tools/adamw_bench.py [--reps 20]"""
+multi-tensor chunk sizes (elements per workgroup).  usage: python tools/adamw_bench.py [--reps 20]
+
+--clip times, on the same parameter set and interleaved rep by rep in one process, three forms of the optimizer
+step: FusedAdamW unclipped, FusedAdamW(max_grad_norm=1.0) (norm kernel + finish + clipped update, no host sync), and
+today's alternative torch.nn.utils.clip_grad_norm_ followed by the unclipped FusedAdamW; plus the norm kernel and the
+AdamW kernel alone with their achieved TB/s (4 B and 30 B per element)."""
 import argparse
 import os
 import sys
@@ -9,10 +14,111 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "vision-transformer_amd"))
 
 
+def _timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3
+
+
+def _stats(ts):
+    ts = sorted(ts)
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def clip_bench(reps, warmup=3):
+    from VisionTransformer import _ops, config, vit
+    from VisionTransformer.optim import FusedAdamW
+    dev = torch.device("cuda", 0)
+    cfg = config.ViTConfig.preset("base", img_size=224, batch_size=256, num_classes=1000, device="cpu")
+    shapes = [p.shape for p in vit.VisionTransformer(cfg).parameters()]
+    n = sum(s.numel() for s in shapes)
+    torch.manual_seed(0)
+
+    def params():
+        # the gradients as the engine hands them over: views of one flat buffer
+        flat = torch.randn(n, device=dev)
+        ps, off = [], 0
+        for s in shapes:
+            p = torch.nn.Parameter(torch.randn(s, device=dev) * 0.02)
+            p.grad = flat[off:off + s.numel()].view(s)
+            off += s.numel()
+            ps.append(p)
+        return ps, flat
+
+    arms = {}
+    for name, clip in (("unclipped", None), ("fused_clipped", 1.0), ("clip_grad_norm_+step", None)):
+        ps, flat = params()
+        arms[name] = (ps, flat, FusedAdamW(ps, lr=1e-4, weight_decay=1e-4, max_grad_norm=clip))
+
+    def run(name):
+        ps, flat, opt = arms[name]
+        flat.normal_()                  # every arm redraws its gradients (untimed): clipping in place shrinks them
+        torch.cuda.synchronize()
+        if name == "clip_grad_norm_+step":
+            return _timed(lambda: (torch.nn.utils.clip_grad_norm_(ps, 1.0), opt.step()))
+        return _timed(opt.step)
+
+    times = {k: [] for k in arms}
+    for i in range(reps + warmup):
+        for name in arms:               # interleaved: box drift hits every arm alike
+            t = run(name)
+            if i >= warmup:
+                times[name].append(t)
+    print(f"C2 parameter set: {len(shapes)} tensors, {n / 1e6:.1f}M elements; {reps} reps after {warmup} warm-up, "
+          "device events around the whole step (host launches included), us: median [min .. max]")
+    for name, ts in times.items():
+        print("  %-22s %8.1f [%8.1f .. %8.1f]" % ((name,) + _stats(ts)))
+    med = {k: _stats(v)[0] for k, v in times.items()}
+    print(f"  fused clipped - unclipped: {med['fused_clipped'] - med['unclipped']:+.1f} us;  "
+          f"clip_grad_norm_+step - fused clipped: {med['clip_grad_norm_+step'] - med['fused_clipped']:+.1f} us "
+          f"({med['clip_grad_norm_+step'] / med['fused_clipped']:.2f}x)")
+    # the kernels on one table, timed where they run: the unclipped update back to back, and the clipped step's
+    # three launches in sequence with an event between each (a kernel timed after a different predecessor finds
+    # different lines in the last-level cache)
+    ps, flat, _ = arms["unclipped"]
+    ms, vs = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+    sh = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) for p in ps]
+    tab, nc = _ops.build_chunk_table([(p.detach(), p.grad, m, v, s) for p, m, v, s in zip(ps, ms, vs, sh)], dev)
+    partial = torch.empty(nc, dtype=torch.float64, device=dev)
+    clip = torch.zeros(4, device=dev)
+    adam = (1e-4, 0.9, 0.999, 1e-8, 1e-4, 0.1, 0.001, 1.0, torch.bfloat16)
+    seq = [("grad_sumsq", 4, lambda: _ops.grad_sumsq(tab, nc, 1.0, partial)),
+           ("grad_clip_finish", 0, lambda: _ops.grad_clip_finish(partial, nc, 1.0, clip)),
+           ("adamw_clipped", 30, lambda: _ops.adamw(tab, nc, *adam, clip=clip))]
+    kt = {k: [] for k in ["adamw"] + [k for k, _, _ in seq] + ["clipped sequence"]}
+    for i in range(reps + warmup):
+        t = _timed(lambda: _ops.adamw(tab, nc, *adam))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(seq) + 1)]
+        ev[0].record()
+        for j, (_, _, fn) in enumerate(seq):
+            fn()
+            ev[j + 1].record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            kt["adamw"].append(t)
+            for j, (k, _, _) in enumerate(seq):
+                kt[k].append(ev[j].elapsed_time(ev[j + 1]) * 1e3)
+            kt["clipped sequence"].append(ev[0].elapsed_time(ev[-1]) * 1e3)
+    print(f"kernels ({nc} workgroups; event to event, so each figure includes a launch gap), us: median [min .. max], "
+          "achieved TB/s at the median")
+    bpe = dict([("adamw", 30), ("clipped sequence", 34)] + [(k, b) for k, b, _ in seq])
+    for k, ts in kt.items():
+        m_, lo, hi = _stats(ts)
+        bw = f"{n * bpe[k] / m_ / 1e6:5.2f} TB/s ({bpe[k]} B / element)" if bpe[k] else "one workgroup"
+        print("  %-22s %8.1f [%8.1f .. %8.1f]  %s" % (k, m_, lo, hi, bw))
+    print(f"  norm {float(clip[0]):.3f} coef {float(clip[1]):.3e} skip {float(clip[2]):.0f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--clip", action="store_true", help="time the unclipped, fused-clipped and clip_grad_norm_ steps")
     args = ap.parse_args()
+    if args.clip:
+        return clip_bench(args.reps)
     from VisionTransformer import _ops, config, vit
     dev = torch.device("cuda", 0)
     cfg = config.ViTConfig.preset("base", img_size=224, batch_size=256, num_classes=1000, device="cpu")

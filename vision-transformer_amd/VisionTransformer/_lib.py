@@ -10,7 +10,7 @@ import os
 import torch  # noqa: F401  (must be imported first: provides the HIP runtime the library binds to)
 
 LIB_PATH = os.environ.get("VIT_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvit_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 F32, BF16, MASK4 = 0, 1, 2
 FLAG_SHARED_CUS = 1          # VIT_FLAG_SHARED_CUS (vit_hip.h)
@@ -92,6 +92,9 @@ _SIGS = {
     "vit_resize_to_tensor": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I64, _P, _I32, _P, _I64, _P]),
     "vit_adamw": (ctypes.c_int, [_P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I32, _P]),
     "vit_pack": (ctypes.c_int, [_P, _I64, _I32, _P]),
+    "vit_grad_sumsq": (ctypes.c_int, [_P, _I64, _F, _P, _P]),
+    "vit_grad_clip_finish": (ctypes.c_int, [_P, _I64, _F, _P, _P]),
+    "vit_adamw_clipped": (ctypes.c_int, [_P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I32, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -326,9 +326,44 @@ def softmax_xent(logits, labels, stream=None):
 
 
 def adamw(table_dev, nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale,
-          shadow_dtype, stream=None):
-    _lib.call("vit_adamw", _ptr(table_dev), nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2,
-              grad_scale, dtype_code(shadow_dtype), _stream(stream))
+          shadow_dtype, stream=None, clip=None):
+    """vit_adamw; with `clip` (the [4] f32 device block grad_clip_finish wrote) vit_adamw_clipped: the gradient
+    scale is multiplied by clip[1] on the device and nothing is updated when clip[2] is set."""
+    if clip is None:
+        _lib.call("vit_adamw", _ptr(table_dev), nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2,
+                  grad_scale, dtype_code(shadow_dtype), _stream(stream))
+        return
+    _check_clip(clip)
+    _lib.call("vit_adamw_clipped", _ptr(table_dev), nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1,
+              bias_corr2, grad_scale, dtype_code(shadow_dtype), _ptr(clip), _stream(stream))
+
+
+def _check_clip(clip):
+    _need_cuda(clip)
+    if clip.dtype != torch.float32 or clip.numel() < 4 or not clip.is_contiguous():
+        raise ValueError("clip state must be a contiguous float32 tensor of at least 4 elements")
+
+
+def grad_sumsq(table_dev, nchunks, grad_scale, partial, stream=None):
+    """partial[i] = sum over chunk i of (grad_scale * g)^2, fp64 (vit_grad_sumsq).  `partial`: float64 device tensor
+    (or a slice of one) of at least nchunks elements."""
+    _need_cuda(partial)
+    if partial.dtype != torch.float64 or partial.numel() < nchunks or not partial.is_contiguous():
+        raise ValueError(f"partial must be a contiguous float64 tensor of at least {nchunks} elements")
+    _lib.call("vit_grad_sumsq", _ptr(table_dev), nchunks, grad_scale, _ptr(partial), _stream(stream))
+
+
+def grad_clip_finish(partial, nparts, max_norm, clip, skip_nonfinite=True, stream=None):
+    """clip[0..4) = (norm, coef, skip, skipped total += skip) from partial[0..nparts) (vit_grad_clip_finish).
+    `skip_nonfinite=False` passes -max_norm: the bound is the same and a non-finite norm is not skipped."""
+    _need_cuda(partial)
+    _check_clip(clip)
+    if max_norm is None or not max_norm > 0:
+        raise ValueError(f"max_norm must be a positive number (got {max_norm!r})")
+    if partial.dtype != torch.float64 or partial.numel() < nparts:
+        raise ValueError(f"partial must be a float64 tensor of at least {nparts} elements")
+    _lib.call("vit_grad_clip_finish", _ptr(partial), nparts, max_norm if skip_nonfinite else -max_norm, _ptr(clip),
+              _stream(stream))
 
 
 def pack(table_dev, nchunks, shadow_dtype, stream=None):

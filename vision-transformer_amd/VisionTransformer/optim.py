@@ -26,22 +26,86 @@ class FusedAdamW(torch.optim.Optimizer):
     (bumped by load_state_dict / add_param_group / fresh state) is unchanged and every parameter still has the very
     same .grad tensor object, the same moment tensor objects and every parameter the storage it was tabled with, so
     `p.data = other` or a replaced moment tensor rebuilds the table by itself (one data_ptr() per parameter per step,
-    no per-step pointer signature of gradients and moments)."""
+    no per-step pointer signature of gradients and moments).
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
+    Gradient clipping (`max_grad_norm`, off by default; the reference has none, train.py:94-96).  With a positive
+    `max_grad_norm` the step clips by the global L2 norm of grad_scale * grad over every parameter with a gradient
+    in every param group, as `torch.nn.utils.clip_grad_norm_(params, max_grad_norm)` followed by the plain step
+    would, without a pass that rewrites the gradients and without a host sync: a norm kernel over the same chunk
+    tables, a one-workgroup finish that leaves (norm, coef, skip, skipped total) in device memory, and the AdamW
+    kernel reading coef and skip from there.  `max_grad_norm` is an attribute like `grad_scale`, not a
+    `param_groups` key, so `state_dict()` stays interchangeable with torch AdamW.  `grad_norm()` and
+    `skipped_steps()` return device copies of the last step's norm and the count of skipped steps.
+    `skip_nonfinite` (default on): a step whose norm is inf or NaN changes no parameter, moment or shadow; off, the
+    non-finite coefficient reaches the update as it would in torch.  Deviation: the host never learns of a skip, so
+    the `step` counters advance on a skipped step too, and the bias corrections of later steps are those of step
+    t + 1."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
+                 max_grad_norm=None, skip_nonfinite=True):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid AdamW hyper-parameters")
+        _check_max_grad_norm(max_grad_norm)
         self._version = 0
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = grad_scale
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
         self._tables = {}
         self._steps = {}          # group index -> (params list, steps tensor [n] f32 CPU, host list of ints)
+        self._partial = None      # f64 [chunks of every table]: the norm pass's per-chunk sums
+        self._clip = None         # f32 [4] device: norm, coef, skip, skipped total (vit_grad_clip_finish)
 
     def invalidate(self):
-        """Drop every cached chunk table and step mirror (parameters re-pointed outside any engine)."""
+        """Drop every cached chunk table, the norm pass's partial buffer and the step mirror (parameters re-pointed
+        outside any engine).  The 4-float clip state stays: it points at nothing, and it carries the skipped-step
+        count."""
         self._version += 1
         self._tables = {}
         self._steps = {}
+        self._partial = None
+
+    # ---- gradient clipping --------------------------------------------------------------------------------------
+    def _clip_state(self, device=None):
+        if device is None:
+            device = next(p.device for g in self.param_groups for p in g["params"])
+        if self._clip is None or self._clip.device != device:
+            self._clip = torch.zeros(4, dtype=torch.float32, device=device)
+        return self._clip
+
+    def grad_norm(self):
+        """The last clipped step's global gradient norm (before clipping): a fresh 0-d device tensor, copied on the
+        current stream, so a caller can keep one per step and read them all later without a sync in between."""
+        return self._clip_state()[0].clone()
+
+    def skipped_steps(self):
+        """How many steps were skipped for a non-finite norm so far: a fresh 0-d device tensor, as grad_norm()."""
+        return self._clip_state()[3].clone()
+
+    def _clipped_launch(self, work):
+        """grad_sumsq per table into consecutive slices of one partial buffer, one finish, the clipped update per
+        table — all on the current stream, which the engine's backward() has already made wait for the weight-
+        gradient stream and the all-reduce handles."""
+        _check_max_grad_norm(self.max_grad_norm)
+        device = work[0][5]
+        if any(w[5] != device for w in work):
+            raise RuntimeError("FusedAdamW: a global gradient norm needs every parameter on one device")
+        total = sum(w[1] for w in work)
+        if self._partial is None or self._partial.device != device or self._partial.numel() < total:
+            self._partial = torch.empty(total, dtype=torch.float64, device=device)
+        clip = self._clip_state(device)
+        off = 0
+        for dev_tab, n, *_ in work:
+            _ops.grad_sumsq(dev_tab, n, self.grad_scale, self._partial[off:off + n])
+            off += n
+        _ops.grad_clip_finish(self._partial, total, self.max_grad_norm, clip, self.skip_nonfinite)
+        for dev_tab, n, sdt, group, t, _ in work:
+            self._adamw(dev_tab, n, sdt, group, t, clip)
+
+    def _adamw(self, dev_tab, n, sdt, group, t, clip=None):
+        b1, b2 = group["betas"]
+        _ops.adamw(dev_tab, n, group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t,
+                   1.0 - b2 ** t, self.grad_scale, sdt, clip=clip)
 
     # ---- step counters ------------------------------------------------------------------------------------------
     def _step_state(self, gi, group):
@@ -72,6 +136,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        clipped, work = self.max_grad_norm is not None, []
         for gi, group in enumerate(self.param_groups):
             ps_all = group["params"]
             idx = [i for i, p in enumerate(ps_all) if p.grad is not None]
@@ -102,7 +167,6 @@ class FusedAdamW(torch.optim.Optimizer):
             for i in idx:
                 host[i] += 1
                 by_step.setdefault(host[i], []).append(ps_all[i])
-            b1, b2 = group["betas"]
             for t, ps in by_step.items():
                 # one table for the whole group while every parameter has the same step count, else one per count
                 key = (gi, "all") if len(by_step) == 1 else (gi, "t", t)
@@ -127,8 +191,12 @@ class FusedAdamW(torch.optim.Optimizer):
                            [p.grad.data_ptr() for p in ps])
                     self._tables[key] = tab
                 dev_tab, n, sdt = tab[4], tab[5], tab[6]
-                _ops.adamw(dev_tab, n, group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t,
-                           1.0 - b2 ** t, self.grad_scale, sdt)
+                if clipped:      # the norm spans every table: launch once they all exist
+                    work.append((dev_tab, n, sdt, group, t, ps[0].device))
+                else:
+                    self._adamw(dev_tab, n, sdt, group, t)
+        if work:
+            self._clipped_launch(work)
         return loss
 
     def _table_valid(self, tab, ps):
@@ -172,12 +240,60 @@ def cross_entropy(logits, labels):
     return _XentFn.apply(logits, labels)
 
 
-def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda"):
+def _check_max_grad_norm(max_grad_norm):
+    if max_grad_norm is not None and not (0 < max_grad_norm < math.inf):
+        raise ValueError(f"max_grad_norm must be None or a positive finite number (got {max_grad_norm!r})")
+
+
+class ClippedAdamW(torch.optim.AdamW):
+    """The host path's counterpart of FusedAdamW(max_grad_norm=...): torch.optim.AdamW whose step() first runs
+    torch.nn.utils.clip_grad_norm_ over every parameter with a gradient, and with `skip_nonfinite` leaves parameters
+    and state alone when that norm is inf or NaN (the gradients are still scaled by the non-finite step's
+    coefficient, as clip_grad_norm_ does; zero_grad() discards them).  `max_grad_norm` is an attribute, not a
+    `param_groups` key: state_dict() is torch AdamW's."""
+
+    def __init__(self, params, max_grad_norm, skip_nonfinite=True, **kwargs):
+        _check_max_grad_norm(max_grad_norm)
+        if max_grad_norm is None:
+            raise ValueError("ClippedAdamW needs a max_grad_norm; use torch.optim.AdamW to train unclipped")
+        super().__init__(params, **kwargs)
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
+        self._norm = torch.zeros(())
+        self._skipped = 0
+
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not params:
+            return loss
+        self._norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm).detach().clone()
+        if self.skip_nonfinite and not bool(torch.isfinite(self._norm)):
+            self._skipped += 1
+            return loss
+        super().step()
+        return loss
+
+    def grad_norm(self):
+        return self._norm.clone()
+
+    def skipped_steps(self):
+        return torch.tensor(float(self._skipped))
+
+
+def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda", max_grad_norm=None, skip_nonfinite=True):
     """The reference's optimizer (train.py:66, AdamW(lr, weight_decay=1e-4)): FusedAdamW on a ROCm device,
-    torch.optim.AdamW on the host path."""
+    torch.optim.AdamW on the host path.  `max_grad_norm` (not in the reference) clips by global gradient norm inside
+    the step: FusedAdamW's own keyword on the device, ClippedAdamW on the host."""
     if torch.device(device).type == "cpu":
-        return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
-    return FusedAdamW(params, lr=lr, weight_decay=weight_decay)
+        if max_grad_norm is None:
+            return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
+        return ClippedAdamW(params, max_grad_norm, skip_nonfinite, lr=lr, weight_decay=weight_decay)
+    return FusedAdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                      skip_nonfinite=skip_nonfinite)
 
 
 class CrossEntropyLoss(nn.Module):

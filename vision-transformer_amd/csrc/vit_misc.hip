@@ -1,6 +1,7 @@
 // Memory-bound kernels of the ViT step: patch im2col, CLS rows, column sums, strided copies, dropout backward,
-// GELU, softmax cross-entropy, and the multi-tensor AdamW / shadow-weight pack.  All vectorised where the shape
-// allows (8-16 B per lane), grid-stride, fixed reduction order (bitwise reproducible).
+// GELU, softmax cross-entropy, the multi-tensor AdamW / shadow-weight pack and the gradient norm of its clipped
+// form.  All vectorised where the shape allows (8-16 B per lane), grid-stride, fixed reduction order (bitwise
+// reproducible).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -352,10 +353,8 @@ __global__ __launch_bounds__(256) void xent_reduce_kernel(const float* __restric
 // per lane per step (16-B accesses measured no faster: the update runs at ~5.8 TB/s over 30 B per element).
 // ---------------------------------------------------------------------------------------------------------------
 template <class TS>
-__global__ __launch_bounds__(256) void adamw_kernel(const vit_tensor_chunk* __restrict__ tab, float lr, float b1,
-                                                    float b2, float eps, float wd, float step_size,
-                                                    float inv_sqrt_bc2, float gscale) {
-  const vit_tensor_chunk ch = tab[blockIdx.x];
+VIT_DEV void adamw_chunk(const vit_tensor_chunk ch, float lr, float b1, float b2, float eps, float wd,
+                         float step_size, float inv_sqrt_bc2, float gscale) {
   const float decay = 1.0f - lr * wd;
   for (int64_t t = threadIdx.x; t < ch.n; t += 256) {
     float g = ch.g[t] * gscale;
@@ -373,10 +372,116 @@ __global__ __launch_bounds__(256) void adamw_kernel(const vit_tensor_chunk* __re
 }
 
 template <class TS>
+__global__ __launch_bounds__(256) void adamw_kernel(const vit_tensor_chunk* __restrict__ tab, float lr, float b1,
+                                                    float b2, float eps, float wd, float step_size,
+                                                    float inv_sqrt_bc2, float gscale) {
+  adamw_chunk<TS>(tab[blockIdx.x], lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale);
+}
+
+template <class TS>
 __global__ __launch_bounds__(256) void pack_kernel(const vit_tensor_chunk* __restrict__ tab) {
   const vit_tensor_chunk ch = tab[blockIdx.x];
   if (!ch.shadow) return;
   for (int64_t t = threadIdx.x; t < ch.n; t += 256) st1<TS>((TS*)ch.shadow + t, ch.p[t]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Global-norm gradient clipping (vit_hip.h "Gradient clipping"): a norm pass over the AdamW chunk table, a one-
+// workgroup finish that turns the per-chunk sums into (norm, coef, skip), and the AdamW update reading coef / skip
+// from device memory.  Everything accumulates in fp64 in a fixed order: no atomics, bitwise reproducible.
+// ---------------------------------------------------------------------------------------------------------------
+VIT_DEV double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Sum over the 256 threads of a workgroup, valid in thread 0: wave butterflies, then the 4 wave sums in wave order.
+VIT_DEV double block_sum_f64(double v, double* red /* LDS [4] */) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+VIT_DEV double sq_f64(float g, float gs) {
+  const double d = (double)(g * gs);      // the fp32 product the update itself forms
+  return d * d;
+}
+
+// partial[chunk] = sum over the chunk of (gs * g[t])^2.  A pure read stream: where the chunk's gradient pointer is
+// 16-B aligned each lane issues GS_UNROLL 16-B loads before it consumes the first (all of a lane's loads for the 8 Ki
+// chunk in one batch), unconditionally, so none is branched around; any other base (views of a flat buffer are only
+// 4-B aligned) and the last n % 4 elements go by dword.  A lane adds its elements in index order.  The table hands
+// the pointer over through memory, so it is cast to the global address space here: global_load, not flat_load.
+constexpr int GS_UNROLL = 8;
+typedef const float __attribute__((address_space(1))) * gs_gptr;
+typedef const f32x4 __attribute__((address_space(1))) * gs_gptr4;
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const vit_tensor_chunk* __restrict__ tab, float gs,
+                                                         double* __restrict__ partial) {
+  __shared__ double red[4];
+  const vit_tensor_chunk ch = tab[blockIdx.x];
+  const gs_gptr g = (gs_gptr)ch.g;
+  double acc = 0.0;
+  int64_t done = 0;                       // elements [0, done) are covered by the 16-B loop
+  if ((reinterpret_cast<uintptr_t>(ch.g) & 15) == 0) {
+    const gs_gptr4 g4 = (gs_gptr4)ch.g;
+    const int64_t n4 = ch.n >> 2;
+    int64_t i = threadIdx.x;
+    for (; i + (GS_UNROLL - 1) * 256 < n4; i += GS_UNROLL * 256) {
+      f32x4 x[GS_UNROLL];
+#pragma unroll
+      for (int u = 0; u < GS_UNROLL; ++u) x[u] = g4[i + u * 256];
+#pragma unroll
+      for (int u = 0; u < GS_UNROLL; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc += sq_f64(x[u][j], gs);
+    }
+    for (; i < n4; i += 256) {
+      const f32x4 x = g4[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc += sq_f64(x[j], gs);
+    }
+    done = n4 << 2;
+  }
+  for (int64_t t = done + threadIdx.x; t < ch.n; t += 256) acc += sq_f64(g[t], gs);
+  acc = block_sum_f64(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+// clip[0] = norm, clip[1] = coef, clip[2] = skip, clip[3] += skip.  Thread t adds partial[t], partial[t + 256], ...
+// in that order, then the fixed tree: the order depends on n only through how many terms each thread has.
+// max_norm < 0 selects torch's behaviour for a non-finite norm (|max_norm| is the bound): no skip, and the
+// coefficient (0 for an infinite norm, NaN for a NaN one) reaches the update.
+__global__ __launch_bounds__(256) void grad_clip_finish_kernel(const double* __restrict__ partial, int64_t n,
+                                                               float max_norm, float* __restrict__ clip) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) acc += partial[i];
+  acc = block_sum_f64(acc, red);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(acc);
+  const bool finite = fabsf(norm) <= 3.402823466e+38f;      // false for inf and for NaN
+  const bool skip = !finite && max_norm > 0.f;
+  float coef = fabsf(max_norm) / (norm + 1e-6f);
+  if (coef > 1.f) coef = 1.f;                               // a NaN stays NaN, as torch.clamp(max=1) leaves it
+  if (skip) coef = 0.f;
+  clip[0] = norm;
+  clip[1] = coef;
+  clip[2] = skip ? 1.f : 0.f;
+  clip[3] += skip ? 1.f : 0.f;
+}
+
+// The AdamW update with the gradient scale multiplied by clip[1] (coef), and no access to p / m / v / shadow at all
+// when clip[2] (skip) is set.  A kernel of its own, so adamw_kernel keeps its arguments and its code.
+template <class TS>
+__global__ __launch_bounds__(256) void adamw_clipped_kernel(const vit_tensor_chunk* __restrict__ tab, float lr,
+                                                            float b1, float b2, float eps, float wd, float step_size,
+                                                            float inv_sqrt_bc2, float gscale,
+                                                            const float* __restrict__ clip) {
+  if (clip[2] != 0.f) return;
+  adamw_chunk<TS>(tab[blockIdx.x], lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale * clip[1]);
 }
 
 }  // namespace
@@ -594,6 +699,39 @@ extern "C" int vit_adamw(const vit_tensor_chunk* table_dev, int64_t nchunks, flo
     adamw_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, lr, beta1, beta2, eps, weight_decay, step_size,
                                                           inv_sqrt_bc2, grad_scale);
   return vit::check_launch("vit_adamw");
+}
+
+extern "C" int vit_grad_sumsq(const vit_tensor_chunk* table_dev, int64_t nchunks, float grad_scale, double* partial,
+                              void* stream) {
+  VIT_REQUIRE(table_dev && partial && nchunks > 0, "vit_grad_sumsq: bad arguments");
+  grad_sumsq_kernel<<<(unsigned)nchunks, 256, 0, VIT_STREAM(stream)>>>(table_dev, grad_scale, partial);
+  return vit::check_launch("vit_grad_sumsq");
+}
+
+extern "C" int vit_grad_clip_finish(const double* partial, int64_t nparts, float max_norm, float* clip,
+                                    void* stream) {
+  VIT_REQUIRE(partial && clip && nparts > 0, "vit_grad_clip_finish: bad arguments");
+  VIT_REQUIRE(max_norm < 0.f || max_norm > 0.f, "vit_grad_clip_finish: max_norm must be nonzero (got %g)",
+              (double)max_norm);
+  grad_clip_finish_kernel<<<1, 256, 0, VIT_STREAM(stream)>>>(partial, nparts, max_norm, clip);
+  return vit::check_launch("vit_grad_clip_finish");
+}
+
+extern "C" int vit_adamw_clipped(const vit_tensor_chunk* table_dev, int64_t nchunks, float lr, float beta1,
+                                 float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
+                                 float grad_scale, int32_t shadow_dtype, const float* clip, void* stream) {
+  VIT_REQUIRE(table_dev && clip && nchunks > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f,
+              "vit_adamw_clipped: bad arguments");
+  const float step_size = lr / bias_corr1;
+  const float inv_sqrt_bc2 = 1.0f / sqrtf(bias_corr2);
+  hipStream_t s = VIT_STREAM(stream);
+  if (shadow_dtype == VIT_BF16)
+    adamw_clipped_kernel<bf16_t><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, lr, beta1, beta2, eps, weight_decay,
+                                                                   step_size, inv_sqrt_bc2, grad_scale, clip);
+  else
+    adamw_clipped_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, lr, beta1, beta2, eps, weight_decay,
+                                                                  step_size, inv_sqrt_bc2, grad_scale, clip);
+  return vit::check_launch("vit_adamw_clipped");
 }
 
 extern "C" int vit_pack(const vit_tensor_chunk* table_dev, int64_t nchunks, int32_t shadow_dtype, void* stream) {

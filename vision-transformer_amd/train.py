@@ -192,7 +192,7 @@ def _rank_world():
 
 
 def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkpoint_dir, lr=1e-4,
-          log_every=1, max_steps=None, reference_loop=False):
+          log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None):
     """The reference training loop (train.py:60-119) on the HIP path.  Returns the last epoch's summed loss.
 
     Defaults keep the GPU busy: no host sync inside the epoch — the epoch loss is summed on the device and the per-step
@@ -202,19 +202,26 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     gate is commented out, train.py:114), `iteration` restarting at 0 on resume (train.py:67; the checkpoint's `step`
     is not read back) and the epoch loss as the host sum of each step's loss.item() (train.py:97-99: one host sync
     per step).  Under data parallelism a DistributedSampler gets `set_epoch(epoch)` every epoch and `evaluate`
-    all-reduces its counts."""
+    all-reduces its counts.
+
+    `max_grad_norm` (not in the reference, whose loop has no clipping, train.py:94-96): clip by global gradient norm
+    inside the optimizer step (optim.make_optimizer).  "GradNorm/train_batch" — the norm before clipping — is then
+    logged at the loss's cadence and, like it, stays on the device until the epoch ends (`reference_loop`: per step,
+    with its sync); rank 0 prints how many steps the epoch skipped for a non-finite norm."""
     rank, world = _rank_world()
     saved_epoch = search_checkpoint(checkpoint_dir)
     torch.manual_seed(0)                              # identical init on every rank
     model = vit.VisionTransformer(configs)
-    optimizer = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=device)
+    optimizer = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=device,
+                               max_grad_norm=max_grad_norm)
     iteration = 0
     if saved_epoch is not None:
         print(f"Checkpoint Found. Loading model from epoch {saved_epoch}")
         ckpt = torch.load(os.path.join(checkpoint_dir, f"{saved_epoch}.pt"), map_location="cpu", weights_only=True)
         model.load_state_dict(ckpt["model_state_dict"])
         model = model.to(device)
-        optimizer = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=device)
+        optimizer = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=device,
+                                   max_grad_norm=max_grad_norm)
         optimizer.load_state_dict(ckpt["optimizer_state_dict"])
         iteration = 0 if reference_loop else int(ckpt.get("step", 0))
     else:
@@ -231,11 +238,14 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
             model.enable_data_parallel()      # the engine folds the rank into its dropout seed
     writer = _writer(log_dir) if rank == 0 else None
     running_loss = 0.0
+    clip = max_grad_norm is not None
+    skipped_before = 0
     for epoch in range(saved_epoch, epochs + 1):
         _set_epoch(train_loader, epoch)
         loss_sum = torch.zeros((), device=device)
         host_loss = 0.0
         logged = []                                   # (iteration, device loss) written at the epoch's end
+        logged_norm = []                              # (iteration, device gradient norm), likewise
         t0 = time.time()
         nb = 0
         for tensors, labels in train_loader:
@@ -250,10 +260,14 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
                 host_loss += loss.item()
                 if writer is not None:
                     writer.add_scalar("Loss/train_batch", loss.item(), iteration)
+                    if clip:
+                        writer.add_scalar("GradNorm/train_batch", optimizer.grad_norm().item(), iteration)
             else:
                 loss_sum += loss.detach()
                 if writer is not None and log_every and iteration % log_every == 0:
                     logged.append((iteration, loss.detach()))
+                    if clip:
+                        logged_norm.append((iteration, optimizer.grad_norm()))
             iteration += 1
             nb += 1
             if max_steps and nb >= max_steps:
@@ -261,6 +275,9 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
         if logged:
             for (it, _), v in zip(logged, torch.stack([v for _, v in logged]).tolist()):
                 writer.add_scalar("Loss/train_batch", v, it)
+        if logged_norm:
+            for (it, _), v in zip(logged_norm, torch.stack([v for _, v in logged_norm]).tolist()):
+                writer.add_scalar("GradNorm/train_batch", v, it)
         running_loss = host_loss if reference_loop else float(loss_sum.item())
         dt = time.time() - t0
         acc = None
@@ -277,17 +294,23 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
             ips = nb * configs.batch_size * world / max(dt, 1e-9)
             print(f"Epoch {epoch}, curr loss: {running_loss:.4f}, mean_accuracy: {acc}, "
                   f"{nb} steps in {dt:.2f}s ({ips:.1f} img/s over {world} GPU(s))", flush=True)
+            if clip:
+                skipped = int(optimizer.skipped_steps().item())
+                print(f"Epoch {epoch}, steps skipped for a non-finite gradient norm: {skipped - skipped_before}",
+                      flush=True)
+                skipped_before = skipped
     return running_loss
 
 
-def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234):
+def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None):
     """The hot loop body (train.py:91-98: forward, CE loss, zero_grad(set_to_none), backward, AdamW step) on one
     synthetic batch already resident on `dev`, dropout on; returns (seconds per timed step, last loss).  This is the
-    repo's own CPU training step that bench.py's `cpu_baseline` times (BASELINE config 1)."""
+    repo's own CPU training step that bench.py's `cpu_baseline` times (BASELINE config 1).  Unclipped unless
+    `max_grad_norm` is given."""
     dev = torch.device(dev or device)
     torch.manual_seed(0)
     model = vit.VisionTransformer(configs).to(dev).train()
-    opt = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=dev)
+    opt = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=dev, max_grad_norm=max_grad_norm)
     g = torch.Generator().manual_seed(seed)
     n_img = int(round((configs.num_patches ** 0.5) * configs.patch_size))
     x = torch.randn(configs.batch_size, configs.input_channels, n_img, n_img, generator=g).to(dev)
@@ -321,6 +344,9 @@ def main():
     ap.add_argument("--test-size", type=int, default=64)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--eval-iter", type=int, default=1)
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="FLOAT",
+                    help="clip gradients to this global L2 norm inside the optimizer step and log GradNorm/train_batch "
+                         "(default: no clipping, as the reference)")
     ap.add_argument("--reference-loop", action="store_true",
                     help="the reference's loop bookkeeping exactly: validate every epoch, restart the step counter on "
                          "resume, host-summed loss (train.py:60-119)")
@@ -360,7 +386,7 @@ def main():
                            batch_size=args.batch, device="cpu")
     if args.bench:
         steps = args.steps or 30
-        sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr)
+        sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm)
         print(json.dumps({"device": device, "model": args.model, "img": args.img, "batch": args.batch,
                           "dtype": args.dtype, "threads": torch.get_num_threads(), "warmup": args.warmup,
                           "steps": steps, "ms_per_step": round(sec * 1e3, 3),
@@ -402,7 +428,7 @@ def main():
         test_loader = torch.utils.data.DataLoader(test_set, batch_size=args.batch, num_workers=args.workers,
                                                   sampler=tsampler, drop_last=False, pin_memory=pin)
     train(cfg, train_loader, test_loader, args.epochs, args.eval_iter, args.log_dir, args.checkpoint_dir,
-          lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop)
+          lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop, max_grad_norm=args.clip_grad_norm)
     if world > 1:
         dist.destroy_process_group()
 
