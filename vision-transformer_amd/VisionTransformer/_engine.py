@@ -25,6 +25,7 @@ from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
+from torch.optim.optimizer import register_optimizer_step_post_hook
 from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib, _ops
@@ -37,6 +38,29 @@ SHADOWS = WeakIdKeyDictionary()
 
 def shadow_of(p):
     return SHADOWS.get(p)
+
+
+# id(parameter) -> (weak reference to it, weak reference to the engine that captured it): which engines an optimizer
+# step wrote to.  Keyed by id for a plain dict lookup per parameter per step; an entry leaves with its parameter.
+_ENGINE_OF = {}
+
+
+def _after_optimizer_step(optimizer, args, kwargs):
+    """After the step of any optimizer but FusedAdamW, the shadows of the engines it wrote to are stale.  The version
+    counters say so for torch's for-loop and foreach optimizers; its fused ones (`AdamW(fused=True)`, ...) update the
+    parameters in one kernel that bumps no version counter, so ensure_ready() could not tell.  Host work only."""
+    if getattr(optimizer, "refreshes_shadows", False):
+        return
+    for group in optimizer.param_groups:
+        for p in group["params"]:
+            ent = _ENGINE_OF.get(id(p))
+            if ent is not None and ent[0]() is p:
+                eng = ent[1]()
+                if eng is not None:
+                    eng._ver_sig = None
+
+
+register_optimizer_step_post_hook(_after_optimizer_step)
 
 
 DROPOUT_P = 0.2          # transformer.py:35,53 (config.dropout is stored but unused by the reference)
@@ -241,14 +265,35 @@ class Engine:
             p[f"{l}.ln2_w"], p[f"{l}.ln2_b"] = blk.ln2.weight, blk.ln2.bias
         return p
 
+    def _expected_shape(self, name, nc, batch):
+        """Shape the config gives parameter `name` of _collect (the head's width `nc` and the CLS parameter's batch
+        rows are the module's own)."""
+        D, hd = self.D, self.hd
+        short = name.rpartition(".")[2]
+        if short[:1] in ("q", "k", "v") and short[1:].isdigit():
+            return (hd, D)
+        if short in ("proj_b", "fc2_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b", "conv_b"):
+            return (D,)
+        if short in ("fc1_b", "h0_b", "hln_w", "hln_b"):
+            return (4 * D,)
+        return {"conv_w": (D, self.C, self.P, self.P), "cls": (batch, 1, D), "pos": (1, self.T, D),
+                "h0_w": (4 * D, D), "h3_w": (nc, 4 * D), "h3_b": (nc,), "proj_w": (D, D), "fc1_w": (4 * D, D),
+                "fc2_w": (D, 4 * D)}[short]
+
     def _build(self, model, device):
         D, hd, L = self.D, self.hd, self.L
         params = self._collect(model)
+        # the classifier's width follows the head the module holds now (`model.mlp[3] = nn.Linear(4 * D, nc)`, the
+        # fine-tuning recipe); every other shape is fixed by the config, and the kernels trust it
+        self.nc = nc = params["h3_w"].shape[0]
         for n, t in params.items():
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError(f"parameter {n} must be contiguous float32 master weights (got {t.dtype})")
             if t.device != device:
                 raise RuntimeError(f"parameter {n} is on {t.device}, expected {device}; call model.to(device)")
+            if tuple(t.shape) != self._expected_shape(n, nc, t.shape[0]):
+                raise RuntimeError(f"parameter {n} has shape {tuple(t.shape)}, but the config gives "
+                                   f"{self._expected_shape(n, nc, t.shape[0])}")
 
         def shape(name):       # of a region: its parameter's, but for the fused QKV and the conv-as-GEMM matrices
             if name.endswith(".qkv_w"):
@@ -283,6 +328,7 @@ class Engine:
         self.grad_region = []           # gradient region (key of self.gw / self.owners) of each grad view
         self.owners = {}                # which parameters feed each region (a fused QKV region: 3H per-head ones)
         self.pack_entries = []
+        me = weakref.ref(self)
         for name, p in params.items():
             key, rows = name, slice(None)
             l, _, short = name.partition(".")
@@ -296,6 +342,7 @@ class Engine:
             self.grad_region.append(key)
             self.owners.setdefault(key, []).append(p)
             SHADOWS[p] = sv
+            _ENGINE_OF[id(p)] = (weakref.ref(p, lambda _, k=id(p): _ENGINE_OF.pop(k, None)), me)
             if sv is not None:
                 self.pack_entries.append((p, sv))
         self.params = params
@@ -304,6 +351,10 @@ class Engine:
         self._pack_table = None
         self._ptr_sig = self._pointer_signature()
         self._ver_sig = None
+        # the module tree as it stands: every (container dict, key, object) of a submodule or a parameter, for
+        # _tree_changed()
+        self._tree = [(d, k, o) for mod in model.modules() for d in (mod._modules, mod._parameters)
+                      for k, o in d.items()]
 
     def _pointer_signature(self):
         return tuple(p.data_ptr() for p in self.param_list)
@@ -311,12 +362,23 @@ class Engine:
     def _version_signature(self):
         return sum(p._version for p in self.param_list)
 
+    def _tree_changed(self):
+        """Whether the module tree no longer holds the very objects captured at _build: a replaced submodule
+        (`model.mlp[3] = nn.Linear(...)`), a replaced Parameter (`module.weight = nn.Parameter(...)`,
+        `load_state_dict(assign=True)`).  Neither moves a captured parameter's storage or version, so the two
+        signatures cannot see it.  One dict lookup and identity test per submodule and parameter, host only."""
+        for d, k, o in self._tree:
+            if d.get(k) is not o:
+                return True
+        return False
+
     def ensure_ready(self, device):
         model = self.model_ref()
         if model is None or getattr(model, "_engine", None) is not self:
             raise RuntimeError("this engine does not belong to the model it is called for (copied engine?); "
                                "models must build their own engine (VisionTransformer.hip_engine)")
-        if self.params is None or self.device != device or self._pointer_signature() != self._ptr_sig:
+        if (self.params is None or self.device != device or self._tree_changed()
+                or self._pointer_signature() != self._ptr_sig):
             self._build(model, device)
         ver = self._version_signature()
         if ver != self._ver_sig:
@@ -324,16 +386,16 @@ class Engine:
             self._ver_sig = ver
 
     def repack(self):
-        """shadow <- compute-dtype copy of the fp32 master matrices (one multi-tensor launch)."""
+        """shadow <- compute-dtype copy of the fp32 master matrices (one multi-tensor launch).  Before the first
+        forward there is no shadow yet and nothing to do: the first build packs."""
+        if self.params is None:
+            return
         if self._pack_table is None:
             entries = [(p.detach(), None, None, None, sv) for p, sv in self.pack_entries]
             self._pack_table = _ops.build_chunk_table(entries, self.device)
         tab, n = self._pack_table
         _ops.pack(tab, n, self.dtype)
         self.stats["packs"] += 1
-
-    def mark_shadow_fresh(self):
-        self._ver_sig = self._version_signature()
 
     # ------------------------------------------------------------------------------------------------------------
     def _token_rows(self, name, M, D, dt, T, dev):

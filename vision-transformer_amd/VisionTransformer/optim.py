@@ -41,6 +41,10 @@ class FusedAdamW(torch.optim.Optimizer):
     the `step` counters advance on a skipped step too, and the bias corrections of later steps are those of step
     t + 1."""
 
+    # its kernel writes the engines' compute-dtype shadows along with the masters: no repack follows a step
+    # (_engine._after_optimizer_step marks them stale after every other optimizer's)
+    refreshes_shadows = True
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
                  max_grad_norm=None, skip_nonfinite=True):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):

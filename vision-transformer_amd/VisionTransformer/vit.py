@@ -17,9 +17,24 @@ Extra (additive) API:
     (RCCL) bucket-by-bucket while the backward is still running.  Use this instead of wrapping the model in
     `torch.nn.parallel.DistributedDataParallel` (which is detected and refused: the fused engine is one autograd
     node, so DDP's per-parameter reducer hooks would never fire);
-  * `model.hip_engine` — the engine (flat gradient / shadow-weight buffers).  After writing the fp32 parameters
-    out-of-band (through `p.data`, which autograd does not version), call `model.hip_engine.repack()`;
-    `load_state_dict` and in-place writes on the parameters themselves are detected automatically.
+  * `model.hip_engine` — the engine (flat gradient / shadow-weight buffers).  Every forward checks, on the host,
+    that its cached state still belongs to the module's weights, and detects by itself:
+      - in-place writes on the parameters that autograd versions (`p.mul_()` / `p.copy_()` / `nn.init.*` under
+        `no_grad`, writes through `state_dict()` tensors, plain `load_state_dict`, `vector_to_parameters`, torch
+        for-loop / foreach optimizers), and the step of any optimizer other than FusedAdamW, torch's `fused=True`
+        ones included (they bump no version; an optimizer step hook reports them): the shadow weights are
+        repacked;
+      - re-pointed storage (`p.data = t`, `model.to(device)`, `model.double().float()`), by each parameter's
+        address, and replaced objects (`model.mlp[3] = nn.Linear(4 * D, nc)` — `vit_config.num_classes` then
+        follows the new head —, `module.weight = nn.Parameter(...)`, `load_state_dict(assign=True)`), by
+        identity against the module tree: the engine rebuilds its buffers around the current parameters
+        (gradients already accumulated are carried over by the next backward).  A replacement must keep the
+        shape the config gives the parameter, the head's class count apart.
+    NOT detected: in-place writes that bump no version counter — through `p.data` (`p.data.mul_()`,
+    `p.data.copy_()`), and on the device `torch.optim.swa_utils.AveragedModel.update_parameters` after its first
+    call (torch's `_foreach_lerp_` kernel; the first call copies, which is versioned).  Call
+    `model.hip_engine.repack()` after them (a no-op before the first forward, which packs anyway).  Nor storage
+    re-pointed twice between two forwards that lands on the address it started from.
 
 Device semantics (the reference picks 'cuda' or 'cpu', train.py:26): a model on a ROCm device runs the fused HIP
 engine and fails loudly when libvit_hip.so is missing; a model on the CPU runs the host path `_cpu.py` (plain torch
@@ -29,6 +44,7 @@ Gradient semantics kept from the reference module: `requires_grad=False` paramet
 None and their weight-gradient GEMMs are skipped), `x.requires_grad` yields the input gradient, and parameter hooks
 (`register_hook`, `register_post_accumulate_grad_hook`) run once per backward, after the gradients are complete.
 """
+import copy
 import os
 
 import torch
@@ -99,6 +115,25 @@ class VisionTransformer(nn.Module):
         self._anchor = None
 
     @property
+    def vit_config(self):
+        """The config the model was built from, with `num_classes` following the classifier head the module holds
+        now (`model.mlp[3] = nn.Linear(4 * D, nc)`): a model built from it loads this model's state_dict.  The
+        constructor's config object itself, which other models may share, is never written."""
+        d = self.__dict__
+        cfg = d["_vit_config"] if "_vit_config" in d else d["vit_config"]      # (a model pickled before the property)
+        mlp = self._modules.get("mlp")
+        w = getattr(mlp[3], "weight", None) if mlp is not None and len(mlp) > 3 else None
+        if w is not None and w.dim() == 2 and w.shape[0] != cfg.num_classes:
+            cfg = copy.copy(cfg)
+            cfg.num_classes = w.shape[0]
+            d["_vit_config"] = cfg
+        return cfg
+
+    @vit_config.setter
+    def vit_config(self, config):
+        self.__dict__["_vit_config"] = config
+
+    @property
     def hip_engine(self):
         if self._engine is None:
             self._engine = Engine(self)
@@ -141,7 +176,6 @@ class VisionTransformer(nn.Module):
         return state
 
     def __deepcopy__(self, memo):
-        import copy
         cls = self.__class__
         new = cls.__new__(cls)
         memo[id(self)] = new
