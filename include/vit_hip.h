@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VIT_ABI_VERSION 17
+#define VIT_ABI_VERSION 18
 
 typedef enum { VIT_OK = 0, VIT_ERR_INVALID = 1, VIT_ERR_LAUNCH = 2 } vit_status;
 typedef enum { VIT_F32 = 0, VIT_BF16 = 1, VIT_MASK4 = 2 } vit_dtype;
@@ -72,6 +72,7 @@ const char* vit_last_error(void);
  * vs 31.6 ms/step), and its option name "gemm_tail_v2": refused likewise.
  * ABI 17 adds the gradient-clipping entry points (vit_grad_sumsq, vit_grad_clip_finish, vit_adamw_clipped) and no
  * option name: clipping is an argument of the optimizer, not a kernel variant.
+ * ABI 18 adds the weight-EMA entry points (vit_adamw_ema, vit_ema_swap), likewise with no option name.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -323,6 +324,27 @@ int vit_grad_clip_finish(const double* partial, int64_t nparts, float max_norm,
 int vit_adamw_clipped(const vit_tensor_chunk* table_dev, int64_t nchunks, float lr, float beta1, float beta2,
                       float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
                       int32_t shadow_dtype, const float* clip, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Weight EMA kept inside the AdamW step (ABI 18).  The reference has no counterpart (train.py:94-96 steps and
+ * evaluates the raw weights); the recurrence is timm's ModelEmaV2: e_t = e_{t-1} + (1 - decay) * (p_t - e_{t-1}) with
+ * p_t the weights AFTER step t.  The update kernel has p_t in a register when the EMA needs it, so the EMA costs one
+ * more read-modify-write stream (38 B per element instead of 30) and no pass or launch of its own.
+ * The chunk table keeps its layout; the EMA pointers travel in a parallel DEVICE array, one float* per chunk:
+ * ema_dev[i] is the EMA slice of chunk i (n floats, 4-B alignment suffices: it may be a view of a larger buffer),
+ * NULL for a chunk that keeps no EMA.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* vit_adamw (clip == NULL) or vit_adamw_clipped (clip != NULL) followed, for every element of every chunk
+ * whose ema[i] is not NULL, by   e += ema_weight * (p_new - e)   in fp32 (ema_weight = 1 - decay, formed in
+ * double on the host and rounded once).  p, m, v and the shadows are bitwise those of the kernel it extends.
+ * When clip != NULL and clip[2] != 0 (skipped step) nothing is touched, the EMA included. */
+int vit_adamw_ema(const vit_tensor_chunk* table_dev, float* const* ema_dev, int64_t nchunks, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
+                  int32_t shadow_dtype, float ema_weight, const float* clip, void* stream);
+/* For every chunk with ema[i] != NULL: exchange p and e element by element, then shadow = (dtype) p.
+ * Other chunks are not touched.  Applying it twice restores every bit.  Reads the p, shadow and n fields only. */
+int vit_ema_swap(const vit_tensor_chunk* table_dev, float* const* ema_dev, int64_t nchunks, int32_t shadow_dtype,
+                 void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,11 @@ multi-tensor chunk sizes (elements per workgroup).  usage: python tools/adamw_be
 --clip times, on the same parameter set and interleaved rep by rep in one process, three forms of the optimizer
 step: FusedAdamW unclipped, FusedAdamW(max_grad_norm=1.0) (norm kernel + finish + clipped update, no host sync), and
 today's alternative torch.nn.utils.clip_grad_norm_ followed by the unclipped FusedAdamW; plus the norm kernel and the
-AdamW kernel alone with their achieved TB/s (4 B and 30 B per element)."""
+AdamW kernel alone with their achieved TB/s (4 B and 30 B per element).
+
+--ema times, the same way, FusedAdamW plain, FusedAdamW(ema_decay=0.9999) (the EMA inside the one launch) and the plain
+step followed by torch._foreach_lerp_ over separate EMA tensors (what AveragedModel.update_parameters runs); plus the
+EMA kernel and the AdamW kernel alone with their achieved TB/s (38 B and 30 B per element)."""
 import argparse
 import os
 import sys
@@ -112,13 +116,90 @@ def clip_bench(reps, warmup=3):
     print(f"  norm {float(clip[0]):.3f} coef {float(clip[1]):.3e} skip {float(clip[2]):.0f}")
 
 
+def ema_bench(reps, warmup=3, decay=0.9999):
+    from VisionTransformer import _ops, config, vit
+    from VisionTransformer.optim import FusedAdamW
+    dev = torch.device("cuda", 0)
+    cfg = config.ViTConfig.preset("base", img_size=224, batch_size=256, num_classes=1000, device="cpu")
+    shapes = [p.shape for p in vit.VisionTransformer(cfg).parameters()]
+    n = sum(s.numel() for s in shapes)
+    torch.manual_seed(0)
+
+    def params():
+        # the gradients as the engine hands them over: views of one flat buffer
+        flat = torch.randn(n, device=dev)
+        ps, off = [], 0
+        for s in shapes:
+            p = torch.nn.Parameter(torch.randn(s, device=dev) * 0.02)
+            p.grad = flat[off:off + s.numel()].view(s)
+            off += s.numel()
+            ps.append(p)
+        return ps
+
+    arms = {}
+    for name, d in (("plain", None), ("fused_ema", decay), ("step+_foreach_lerp_", None)):
+        ps = params()
+        arms[name] = (ps, FusedAdamW(ps, lr=1e-4, weight_decay=1e-4, ema_decay=d))
+    lerp_ps = [p.detach() for p in arms["step+_foreach_lerp_"][0]]
+    lerp_ema = [p.clone() for p in lerp_ps]
+
+    def run(name):
+        opt = arms[name][1]
+        if name == "step+_foreach_lerp_":
+            return _timed(lambda: (opt.step(), torch._foreach_lerp_(lerp_ema, lerp_ps, 1.0 - decay)))
+        return _timed(opt.step)
+
+    times = {k: [] for k in arms}
+    for i in range(reps + warmup):
+        for name in arms:               # interleaved: box drift hits every arm alike
+            t = run(name)
+            if i >= warmup:
+                times[name].append(t)
+    print(f"C2 parameter set: {len(shapes)} tensors, {n / 1e6:.1f}M elements; {reps} reps after {warmup} warm-up, "
+          "device events around the whole step (host launches included), us: median [min .. max]")
+    for name, ts in times.items():
+        print("  %-22s %8.1f [%8.1f .. %8.1f]" % ((name,) + _stats(ts)))
+    med = {k: _stats(v)[0] for k, v in times.items()}
+    print(f"  fused EMA - plain: {med['fused_ema'] - med['plain']:+.1f} us;  "
+          f"step+_foreach_lerp_ - fused EMA: {med['step+_foreach_lerp_'] - med['fused_ema']:+.1f} us "
+          f"({med['step+_foreach_lerp_'] / med['fused_ema']:.2f}x)")
+    # the two kernels on one table, alternating
+    ps = arms["plain"][0]
+    ms, vs = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+    es = [p.detach().clone() for p in ps]
+    sh = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) for p in ps]
+    tab, nc = _ops.build_chunk_table([(p.detach(), p.grad, m, v, s) for p, m, v, s in zip(ps, ms, vs, sh)], dev)
+    ema_dev, _ = _ops.build_ema_pointers([(p.detach(), e) for p, e in zip(ps, es)], dev)
+    adam = (1e-4, 0.9, 0.999, 1e-8, 1e-4, 0.1, 0.001, 1.0, torch.bfloat16)
+    kern = {"adamw": (30, lambda: _ops.adamw(tab, nc, *adam)),
+            "adamw_ema": (38, lambda: _ops.adamw_ema(tab, ema_dev, nc, *adam, decay)),
+            "ema_swap": (18, lambda: _ops.ema_swap(tab, ema_dev, nc, torch.bfloat16))}
+    kt = {k: [] for k in kern}
+    for i in range(reps + warmup):
+        for k, (_, fn) in kern.items():
+            t = _timed(fn)
+            if i >= warmup:
+                kt[k].append(t)
+        kern["ema_swap"][1]()           # swap back (untimed): the next update sees the weights again
+    print(f"kernels ({nc} workgroups; event to event, so each figure includes a launch gap), us: median [min .. max], "
+          "achieved TB/s at the median")
+    for k, ts in kt.items():
+        m_, lo, hi = _stats(ts)
+        print("  %-22s %8.1f [%8.1f .. %8.1f]  %5.2f TB/s (%d B / element)"
+              % (k, m_, lo, hi, n * kern[k][0] / m_ / 1e6, kern[k][0]))
+    print(f"  adamw_ema / adamw: {_stats(kt['adamw_ema'])[0] / _stats(kt['adamw'])[0]:.3f} (38 / 30 = {38 / 30:.3f})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--clip", action="store_true", help="time the unclipped, fused-clipped and clip_grad_norm_ steps")
+    ap.add_argument("--ema", action="store_true", help="time the plain, fused-EMA and step + _foreach_lerp_ steps")
     args = ap.parse_args()
     if args.clip:
         return clip_bench(args.reps)
+    if args.ema:
+        return ema_bench(args.reps)
     from VisionTransformer import _ops, config, vit
     dev = torch.device("cuda", 0)
     cfg = config.ViTConfig.preset("base", img_size=224, batch_size=256, num_classes=1000, device="cpu")

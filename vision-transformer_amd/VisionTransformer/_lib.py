@@ -10,7 +10,7 @@ import os
 import torch  # noqa: F401  (must be imported first: provides the HIP runtime the library binds to)
 
 LIB_PATH = os.environ.get("VIT_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvit_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 F32, BF16, MASK4 = 0, 1, 2
 FLAG_SHARED_CUS = 1          # VIT_FLAG_SHARED_CUS (vit_hip.h)
@@ -95,6 +95,8 @@ _SIGS = {
     "vit_grad_sumsq": (ctypes.c_int, [_P, _I64, _F, _P, _P]),
     "vit_grad_clip_finish": (ctypes.c_int, [_P, _I64, _F, _P, _P]),
     "vit_adamw_clipped": (ctypes.c_int, [_P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I32, _P, _P]),
+    "vit_adamw_ema": (ctypes.c_int, [_P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I32, _F, _P, _P]),
+    "vit_ema_swap": (ctypes.c_int, [_P, _P, _I64, _I32, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

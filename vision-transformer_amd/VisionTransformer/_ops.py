@@ -395,3 +395,43 @@ def build_chunk_table(entries, device):
     arr = (_lib.TensorChunk * len(chunks))(*chunks)
     host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
     return host.to(device), len(chunks)
+
+
+def build_ema_pointers(entries, device):
+    """The EMA pointer array that goes with build_chunk_table(entries): `entries` is a list of (p, ema) in the same
+    order, ema an fp32 contiguous tensor of p's size (4-B alignment suffices) or None.  One pointer per chunk, cut at
+    the same CHUNK boundaries; 0 (NULL) for every chunk of a tensor without an EMA.  Returns (int64 device tensor,
+    nchunks)."""
+    ptrs = []
+    for p, e in entries:
+        n = p.numel()
+        if e is not None and (e.dtype != torch.float32 or e.numel() != n or not e.is_contiguous()
+                              or e.device != p.device):
+            raise ValueError("an EMA tensor must be contiguous float32 of its parameter's size, on its device")
+        for off in range(0, n, CHUNK):
+            ptrs.append(e.data_ptr() + 4 * off if e is not None else 0)
+    return torch.tensor(ptrs, dtype=torch.int64).to(device), len(ptrs)
+
+
+def _check_ema(ema_dev, nchunks):
+    _need_cuda(ema_dev)
+    if ema_dev.dtype != torch.int64 or ema_dev.numel() != nchunks or not ema_dev.is_contiguous():
+        raise ValueError(f"the EMA pointer array must be a contiguous int64 tensor of {nchunks} elements")
+
+
+def adamw_ema(table_dev, ema_dev, nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale,
+              shadow_dtype, ema_decay, stream=None, clip=None):
+    """vit_adamw_ema: the (clipped, with `clip`) AdamW update, then e += (1 - ema_decay) * (p_new - e) for every chunk
+    whose EMA pointer is set.  The weight 1 - ema_decay is formed in double here and rounded to fp32 once."""
+    _check_ema(ema_dev, nchunks)
+    if clip is not None:
+        _check_clip(clip)
+    _lib.call("vit_adamw_ema", _ptr(table_dev), _ptr(ema_dev), nchunks, lr, beta1, beta2, eps, weight_decay,
+              bias_corr1, bias_corr2, grad_scale, dtype_code(shadow_dtype), 1.0 - float(ema_decay),
+              _ptr(clip), _stream(stream))
+
+
+def ema_swap(table_dev, ema_dev, nchunks, shadow_dtype, stream=None):
+    """vit_ema_swap: p <-> e for every chunk whose EMA pointer is set, and shadow = (dtype) p there."""
+    _check_ema(ema_dev, nchunks)
+    _lib.call("vit_ema_swap", _ptr(table_dev), _ptr(ema_dev), nchunks, dtype_code(shadow_dtype), _stream(stream))

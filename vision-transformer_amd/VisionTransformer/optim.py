@@ -8,6 +8,7 @@ interchangeable with the reference's (train.py:73,110).
 
 CrossEntropyLoss: nn.CrossEntropyLoss() (mean) as one fused softmax + NLL + gradient kernel.
 """
+import contextlib
 import math
 
 import torch
@@ -17,7 +18,45 @@ from . import _ops
 from ._engine import shadow_of
 
 
-class FusedAdamW(torch.optim.Optimizer):
+def _check_ema_decay(ema_decay):
+    if ema_decay is not None and not (0 < ema_decay < 1):
+        raise ValueError(f"ema_decay must be None or lie strictly between 0 and 1 (got {ema_decay!r})")
+
+
+class _EmaSurface:
+    """What FusedAdamW(ema_decay=...) and the host path's EmaAdamW share: the EMA lives in `state[p]["ema"]`, and
+    `swap_ema()` (theirs) exchanges it with the weights."""
+
+    _ema_swapped = False
+
+    def _refuse_step_while_swapped(self):
+        if self._ema_swapped:
+            raise RuntimeError("step() while the EMA weights are swapped in: leave ema_weights() (or call swap_ema() "
+                               "again) first, or the update would train the average and average the raw weights")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the block on the EMA weights: swap them in, and swap the trained weights back in a `finally`."""
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights(): the EMA weights are already swapped in (no nesting)")
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_state_dict(self, model):
+        """`model.state_dict()` with every parameter that has an EMA replaced by a clone of it (read without a swap;
+        while the EMA weights are swapped in, the parameters themselves hold those values)."""
+        out = model.state_dict()
+        for name, p in model.named_parameters():
+            e = self.state[p].get("ema") if p in self.state else None
+            if e is not None and name in out:
+                out[name] = (p if self._ema_swapped else e).detach().clone()
+        return out
+
+
+class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
     """Step bookkeeping stays on the host: each group's per-parameter 'step' entries are 0-d views of ONE CPU
     tensor (torch AdamW's state format, so `state_dict()` / `load_state_dict()` interchange with it), advanced by a
     single in-place add per step, with a host-side mirror of the counts for the bias corrections — no per-parameter
@@ -39,22 +78,37 @@ class FusedAdamW(torch.optim.Optimizer):
     `skip_nonfinite` (default on): a step whose norm is inf or NaN changes no parameter, moment or shadow; off, the
     non-finite coefficient reaches the update as it would in torch.  Deviation: the host never learns of a skip, so
     the `step` counters advance on a skipped step too, and the bias corrections of later steps are those of step
-    t + 1."""
+    t + 1.  With `ema_decay` the EMA does not move on a skipped step either.
+
+    Weight EMA (`ema_decay`, off by default; the reference has none).  With 0 < ema_decay < 1 the same launch keeps an
+    exponential moving average of every stepped parameter in `state[p]["ema"]` (fp32, contiguous): created with the
+    moments as a clone of the weights before the first update, then ema += (1 - ema_decay) * (p_new - ema) after each
+    (timm's ModelEmaV2 order), read and written by the AdamW kernel while p_new is in a register.  A parameter that
+    has moments but no "ema" (a loaded torch AdamW checkpoint) gets one cloned from its value at the next step.
+    `ema_decay` is an attribute, not a `param_groups` key, and may be changed between steps; torch AdamW's
+    load_state_dict carries the extra state key along and its step() ignores it.  `swap_ema()` exchanges weights and
+    EMA in place, shadows included, so the fused engine evaluates the EMA with no repack and no rebuild;
+    `ema_weights()` is the context manager around it (step() raises inside), and `ema_state_dict(model)` reads the
+    EMA out without swapping.  Data parallel needs nothing more: every rank holds bitwise the same gradients after
+    the all-reduce, hence the same weights and the same EMA."""
 
     # its kernel writes the engines' compute-dtype shadows along with the masters: no repack follows a step
     # (_engine._after_optimizer_step marks them stale after every other optimizer's)
     refreshes_shadows = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
-                 max_grad_norm=None, skip_nonfinite=True):
+                 max_grad_norm=None, skip_nonfinite=True, ema_decay=None):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid AdamW hyper-parameters")
         _check_max_grad_norm(max_grad_norm)
+        _check_ema_decay(ema_decay)
         self._version = 0
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = grad_scale
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = skip_nonfinite
+        self.ema_decay = ema_decay
+        self._swap_tables = None  # swap_ema()'s own tables: every parameter with an EMA exactly once
         self._tables = {}
         self._steps = {}          # group index -> (params list, steps tensor [n] f32 CPU, host list of ints)
         self._partial = None      # f64 [chunks of every table]: the norm pass's per-chunk sums
@@ -68,6 +122,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._tables = {}
         self._steps = {}
         self._partial = None
+        self._swap_tables = None
 
     # ---- gradient clipping --------------------------------------------------------------------------------------
     def _clip_state(self, device=None):
@@ -103,11 +158,15 @@ class FusedAdamW(torch.optim.Optimizer):
             _ops.grad_sumsq(dev_tab, n, self.grad_scale, self._partial[off:off + n])
             off += n
         _ops.grad_clip_finish(self._partial, total, self.max_grad_norm, clip, self.skip_nonfinite)
-        for dev_tab, n, sdt, group, t, _ in work:
-            self._adamw(dev_tab, n, sdt, group, t, clip)
+        for dev_tab, n, sdt, group, t, _, ema_dev in work:
+            self._adamw(dev_tab, n, sdt, group, t, clip, ema_dev)
 
-    def _adamw(self, dev_tab, n, sdt, group, t, clip=None):
+    def _adamw(self, dev_tab, n, sdt, group, t, clip=None, ema_dev=None):
         b1, b2 = group["betas"]
+        if self.ema_decay is not None:
+            _ops.adamw_ema(dev_tab, ema_dev, n, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                           1.0 - b1 ** t, 1.0 - b2 ** t, self.grad_scale, sdt, self.ema_decay, clip=clip)
+            return
         _ops.adamw(dev_tab, n, group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t,
                    1.0 - b2 ** t, self.grad_scale, sdt, clip=clip)
 
@@ -140,6 +199,10 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._refuse_step_while_swapped()
+        ema = self.ema_decay is not None
+        if ema:
+            _check_ema_decay(self.ema_decay)
         clipped, work = self.max_grad_norm is not None, []
         for gi, group in enumerate(self.param_groups):
             ps_all = group["params"]
@@ -158,6 +221,9 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["step"] = torch.tensor(0.0)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    fresh = True
+                if ema and "ema" not in st:      # with the moments, or at the first step after a torch checkpoint
+                    st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
                     fresh = True
             if fresh:
                 self.invalidate()
@@ -188,17 +254,22 @@ class FusedAdamW(torch.optim.Optimizer):
                             if not tt.is_contiguous():
                                 raise RuntimeError("FusedAdamW: non-contiguous grad/state")
                     dev_tab, n = _ops.build_chunk_table(entries, ps[0].device)
+                    emas = [self.state[p].get("ema") for p in ps]
+                    if all(e is None for e in emas):
+                        emas = ema_dev = None
+                    else:
+                        ema_dev, _ = _ops.build_ema_pointers(list(zip(ps, emas)), ps[0].device)
                     # entries keep every tabled tensor alive; the raw shadow list is what the identity check compares
                     tab = (self._version, list(ps), [p.grad for p in ps], [shadow_of(p) for p in ps], dev_tab, n,
                            sdt, entries, [p.data_ptr() for p in ps],
                            [(self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in ps],
-                           [p.grad.data_ptr() for p in ps])
+                           [p.grad.data_ptr() for p in ps], emas, ema_dev)
                     self._tables[key] = tab
-                dev_tab, n, sdt = tab[4], tab[5], tab[6]
+                dev_tab, n, sdt, ema_dev = tab[4], tab[5], tab[6], tab[12]
                 if clipped:      # the norm spans every table: launch once they all exist
-                    work.append((dev_tab, n, sdt, group, t, ps[0].device))
+                    work.append((dev_tab, n, sdt, group, t, ps[0].device, ema_dev))
                 else:
-                    self._adamw(dev_tab, n, sdt, group, t)
+                    self._adamw(dev_tab, n, sdt, group, t, None, ema_dev)
         if work:
             self._clipped_launch(work)
         return loss
@@ -208,9 +279,16 @@ class FusedAdamW(torch.optim.Optimizer):
         same moment tensor objects as when the table was built, and no parameter's or gradient's storage moved (`p.data = ...`
         re-points storage without changing any object identity).  Two data_ptr() per parameter plus
         identity checks: this runs every step.  The engine's shadows change only when it rebuilds its buffers, and
-        then every gradient view is a new object too."""
+        then every gradient view is a new object too.  A table built with EMA pointers also wants every parameter's
+        `state[p]["ema"]` to be the tensor object it points at; one built without serves only the EMA-less step."""
         ver, tps, grads, ptrs, moments, gptrs = tab[0], tab[1], tab[2], tab[8], tab[9], tab[10]
         if ver != self._version or len(tps) != len(ps):
+            return False
+        emas = tab[11]
+        if emas is None:      # a table without EMA pointers serves only the EMA-less step (no per-parameter work)
+            if self.ema_decay is not None:
+                return False
+        elif any(self.state[a].get("ema") is not e for a, e in zip(tps, emas)):
             return False
         state = self.state
         for a, b, g, ptr, (m, v), gp in zip(tps, ps, grads, ptrs, moments, gptrs):
@@ -221,6 +299,47 @@ class FusedAdamW(torch.optim.Optimizer):
             if st["exp_avg"] is not m or st["exp_avg_sq"] is not v:
                 return False
         return True
+
+    # ---- weight EMA ---------------------------------------------------------------------------------------------
+    def _ema_swap_tables(self):
+        """Chunk tables for vit_ema_swap: every parameter that has an EMA exactly once, whichever step tables exist
+        (those carry gradient pointers, go stale with zero_grad(set_to_none=True), and two of them may hold the same
+        parameter).  One table per (device, shadow dtype), in practice one.  Reused while the optimizer's version, every
+        parameter's storage, EMA tensor object and shadow object are those it was built from."""
+        state = self.state       # .get: looking must not create an (empty) state entry for a parameter that has none
+        ps = [p for g in self.param_groups for p in g["params"] if (state.get(p) or {}).get("ema") is not None]
+        cached = self._swap_tables
+        if cached is not None and cached[0] == self._version and len(cached[1]) == len(ps) and all(
+                a is b and a.data_ptr() == ptr and self.state[a]["ema"] is e and shadow_of(a) is s
+                for (a, ptr, e, s), b in zip(cached[1], ps)):
+            return cached[2]
+        groups = {}
+        for p in ps:
+            s = shadow_of(p)
+            groups.setdefault((p.device, s.dtype if s is not None else None), []).append((p, self.state[p]["ema"], s))
+        for dev in {d for d, _ in groups}:      # shadow-less parameters ride in their device's first table
+            bare = groups.pop((dev, None), None)
+            if bare:
+                key = next((k for k in groups if k[0] == dev), (dev, torch.float32))
+                groups.setdefault(key, []).extend(bare)
+        tables = []
+        for (dev, sdt), ents in groups.items():
+            if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p, _, _ in ents):
+                raise RuntimeError("FusedAdamW: parameters must be contiguous float32 on a ROCm device")
+            dev_tab, n = _ops.build_chunk_table([(p.detach(), None, None, None, s) for p, _, s in ents], dev)
+            ema_dev, _ = _ops.build_ema_pointers([(p, e) for p, e, _ in ents], dev)
+            tables.append((dev_tab, ema_dev, n, sdt, ents))
+        self._swap_tables = (self._version, [(p, p.data_ptr(), self.state[p]["ema"], shadow_of(p)) for p in ps], tables)
+        return tables
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange every parameter that has an EMA with it, in place, and refresh its compute-dtype shadow from the
+        new value: one launch per table, no repack, no engine rebuild (the engine reads the same buffers).  A second
+        call restores every bit.  Parameters without an EMA are left alone."""
+        for dev_tab, ema_dev, n, sdt, _ in self._ema_swap_tables():
+            _ops.ema_swap(dev_tab, ema_dev, n, sdt)
+        self._ema_swapped = not self._ema_swapped
 
 
 class _XentFn(torch.autograd.Function):
@@ -288,16 +407,85 @@ class ClippedAdamW(torch.optim.AdamW):
         return torch.tensor(float(self._skipped))
 
 
-def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda", max_grad_norm=None, skip_nonfinite=True):
+class EmaAdamW(_EmaSurface, torch.optim.AdamW):
+    """The host path's counterpart of FusedAdamW(ema_decay=...), in torch ops: torch.optim.AdamW whose step() then
+    moves `state[p]["ema"]` by ema += (1 - ema_decay) * (p_new - ema) for every parameter it stepped.  Same
+    initialisation (a clone of the weights before the parameter's first update here), same surface (`ema_decay`
+    attribute, swap_ema(), ema_weights(), ema_state_dict(model)).  With `max_grad_norm` it clips first as ClippedAdamW
+    does, and a step skipped for a non-finite norm leaves the EMA alone too."""
+
+    def __init__(self, params, ema_decay, max_grad_norm=None, skip_nonfinite=True, **kwargs):
+        _check_ema_decay(ema_decay)
+        _check_max_grad_norm(max_grad_norm)
+        if ema_decay is None:
+            raise ValueError("EmaAdamW needs an ema_decay; use torch.optim.AdamW or ClippedAdamW to train without")
+        super().__init__(params, **kwargs)
+        self.ema_decay = ema_decay
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
+        self._norm = torch.zeros(())
+        self._skipped = 0
+
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._refuse_step_while_swapped()
+        _check_ema_decay(self.ema_decay)
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not params:
+            return loss
+        if self.max_grad_norm is not None:
+            self._norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm).detach().clone()
+            if self.skip_nonfinite and not bool(torch.isfinite(self._norm)):
+                self._skipped += 1
+                return loss
+        # torch's step() creates its state only where there is none at all, so a new EMA joins the state after it
+        new = [(p, p.detach().clone(memory_format=torch.contiguous_format)) for p in params
+               if "ema" not in self.state.get(p, ())]
+        super().step()
+        for p, e in new:
+            self.state[p]["ema"] = e
+        w = 1.0 - float(self.ema_decay)
+        with torch.no_grad():
+            for p in params:
+                e = self.state[p]["ema"]
+                e.add_(p.detach() - e, alpha=w)
+        return loss
+
+    @torch.no_grad()
+    def swap_ema(self):
+        for g in self.param_groups:
+            for p in g["params"]:
+                e = self.state[p].get("ema") if p in self.state else None
+                if e is not None:
+                    old = p.detach().clone()
+                    p.copy_(e)
+                    e.copy_(old)
+        self._ema_swapped = not self._ema_swapped
+
+    def grad_norm(self):
+        return self._norm.clone()
+
+    def skipped_steps(self):
+        return torch.tensor(float(self._skipped))
+
+
+def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda", max_grad_norm=None, skip_nonfinite=True,
+                   ema_decay=None):
     """The reference's optimizer (train.py:66, AdamW(lr, weight_decay=1e-4)): FusedAdamW on a ROCm device,
     torch.optim.AdamW on the host path.  `max_grad_norm` (not in the reference) clips by global gradient norm inside
-    the step: FusedAdamW's own keyword on the device, ClippedAdamW on the host."""
+    the step: FusedAdamW's own keyword on the device, ClippedAdamW on the host.  `ema_decay` (not in the reference
+    either) keeps an EMA of the weights inside the step: FusedAdamW's keyword on the device, EmaAdamW on the host."""
     if torch.device(device).type == "cpu":
+        if ema_decay is not None:
+            return EmaAdamW(params, ema_decay, max_grad_norm, skip_nonfinite, lr=lr, weight_decay=weight_decay)
         if max_grad_norm is None:
             return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
         return ClippedAdamW(params, max_grad_norm, skip_nonfinite, lr=lr, weight_decay=weight_decay)
     return FusedAdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                      skip_nonfinite=skip_nonfinite)
+                      skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
 
 
 class CrossEntropyLoss(nn.Module):

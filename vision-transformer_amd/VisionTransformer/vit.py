@@ -35,6 +35,9 @@ Extra (additive) API:
     call (torch's `_foreach_lerp_` kernel; the first call copies, which is versioned).  Call
     `model.hip_engine.repack()` after them (a no-op before the first forward, which packs anyway).  Nor storage
     re-pointed twice between two forwards that lands on the address it started from.
+    An EMA of the weights needs neither `AveragedModel` nor `repack()`: `FusedAdamW(ema_decay=...)` keeps it inside
+    the optimizer's launch, and its `ema_weights()` swaps it in and out of this model's own buffers, shadows included
+    (optim.py).  `AveragedModel` still works, with the `repack()` above.
 
 Device semantics (the reference picks 'cuda' or 'cpu', train.py:26): a model on a ROCm device runs the fused HIP
 engine and fails loudly when libvit_hip.so is missing; a model on the CPU runs the host path `_cpu.py` (plain torch

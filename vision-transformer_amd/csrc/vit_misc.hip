@@ -1,7 +1,7 @@
 // Memory-bound kernels of the ViT step: patch im2col, CLS rows, column sums, strided copies, dropout backward,
-// GELU, softmax cross-entropy, the multi-tensor AdamW / shadow-weight pack and the gradient norm of its clipped
-// form.  All vectorised where the shape allows (8-16 B per lane), grid-stride, fixed reduction order (bitwise
-// reproducible).
+// GELU, softmax cross-entropy, the multi-tensor AdamW / shadow-weight pack, the gradient norm of its clipped
+// form and the weight EMA kept inside it.  All vectorised where the shape allows (8-16 B per lane), grid-stride,
+// fixed reduction order (bitwise reproducible).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -352,21 +352,31 @@ __global__ __launch_bounds__(256) void xent_reduce_kernel(const float* __restric
 // Multi-tensor AdamW: one workgroup per table chunk (the host sets its size: 8 Ki elements, _ops.CHUNK), one element
 // per lane per step (16-B accesses measured no faster: the update runs at ~5.8 TB/s over 30 B per element).
 // ---------------------------------------------------------------------------------------------------------------
-template <class TS>
+// EMA: also e += ema_w * (p_new - e) on the chunk's EMA slice `ema` (vit_hip.h "Weight EMA"), its load issued with the
+// other four ahead of the dependent math.  One body for both forms, so that p / m / v / shadow agree bit for bit.
+template <class TS, bool EMA = false>
 VIT_DEV void adamw_chunk(const vit_tensor_chunk ch, float lr, float b1, float b2, float eps, float wd,
-                         float step_size, float inv_sqrt_bc2, float gscale) {
+                         float step_size, float inv_sqrt_bc2, float gscale, float* ema = nullptr,
+                         float ema_w = 0.f) {
   const float decay = 1.0f - lr * wd;
   for (int64_t t = threadIdx.x; t < ch.n; t += 256) {
     float g = ch.g[t] * gscale;
     float m = ch.m[t], v = ch.v[t], p = ch.p[t];
-    p *= decay;
-    m = b1 * m + (1.0f - b1) * g;
-    v = b2 * v + (1.0f - b2) * g * g;
-    const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
-    p -= step_size * (m / denom);
+    float e = 0.f;
+    if constexpr (EMA) e = ema[t];
+    // p *= decay; m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g; p -= step_size * m / (sqrt(v) inv_sqrt_bc2 + eps),
+    // with the fused multiply-adds spelled out as the compiler had chosen them: left to it, the EMA form's extra
+    // stream changed which products it fused, and with that the bits of m, v and p.  The plain form's last line is
+    // left to the compiler, which keeps that kernel's code what it was; there it fuses exactly the fma written here.
+    m = __builtin_fmaf(b1, m, (1.0f - b1) * g);
+    v = __builtin_fmaf(b2, v, (1.0f - b2) * g * g);
+    const float denom = __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+    if constexpr (EMA) p = __builtin_fmaf(p, decay, -(step_size * (m / denom)));
+    else p = p * decay - step_size * (m / denom);
     ch.m[t] = m;
     ch.v[t] = v;
     ch.p[t] = p;
+    if constexpr (EMA) ema[t] = __builtin_fmaf(ema_w, p - e, e);
     if (ch.shadow) st1<TS>((TS*)ch.shadow + t, p);
   }
 }
@@ -482,6 +492,46 @@ __global__ __launch_bounds__(256) void adamw_clipped_kernel(const vit_tensor_chu
                                                             const float* __restrict__ clip) {
   if (clip[2] != 0.f) return;
   adamw_chunk<TS>(tab[blockIdx.x], lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale * clip[1]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Weight EMA inside the AdamW step (vit_hip.h "Weight EMA"): the update above, then e += w * (p_new - e) while p_new
+// is still in a register — a sixth stream (8 B per element more: 38 instead of 30), no second pass over p.  ema[i] is
+// chunk i's slice of the EMA tensor (only 4-B aligned: it may be a view), NULL for a chunk that keeps none, which then
+// runs adamw_chunk as it is.  clip as in adamw_clipped_kernel, or NULL for the unclipped step.  One element per lane
+// per iteration: adamw_chunk's EMA form.
+// ---------------------------------------------------------------------------------------------------------------
+template <class TS>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(const vit_tensor_chunk* __restrict__ tab,
+                                                        float* const* __restrict__ ema, float lr, float b1, float b2,
+                                                        float eps, float wd, float step_size, float inv_sqrt_bc2,
+                                                        float gscale, float ema_w, const float* __restrict__ clip) {
+  if (clip) {
+    if (clip[2] != 0.f) return;
+    gscale = gscale * clip[1];
+  }
+  const vit_tensor_chunk ch = tab[blockIdx.x];
+  float* const ema_p = ema[blockIdx.x];
+  if (!ema_p) {
+    adamw_chunk<TS>(ch, lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale);
+    return;
+  }
+  adamw_chunk<TS, true>(ch, lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale, ema_p, ema_w);
+}
+
+// p <-> e element by element, shadow = (dtype) new p.  Reads only the p / shadow / n fields of the table.
+template <class TS>
+__global__ __launch_bounds__(256) void ema_swap_kernel(const vit_tensor_chunk* __restrict__ tab,
+                                                       float* const* __restrict__ ema) {
+  const vit_tensor_chunk ch = tab[blockIdx.x];
+  float* const ema_p = ema[blockIdx.x];
+  if (!ema_p) return;
+  for (int64_t t = threadIdx.x; t < ch.n; t += 256) {
+    const float p = ch.p[t], e = ema_p[t];
+    ch.p[t] = e;
+    ema_p[t] = p;
+    if (ch.shadow) st1<TS>((TS*)ch.shadow + t, e);
+  }
 }
 
 }  // namespace
@@ -732,6 +782,35 @@ extern "C" int vit_adamw_clipped(const vit_tensor_chunk* table_dev, int64_t nchu
     adamw_clipped_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, lr, beta1, beta2, eps, weight_decay,
                                                                   step_size, inv_sqrt_bc2, grad_scale, clip);
   return vit::check_launch("vit_adamw_clipped");
+}
+
+extern "C" int vit_adamw_ema(const vit_tensor_chunk* table_dev, float* const* ema_dev, int64_t nchunks, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
+                             float bias_corr2, float grad_scale, int32_t shadow_dtype, float ema_weight,
+                             const float* clip, void* stream) {
+  VIT_REQUIRE(table_dev && ema_dev && nchunks > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f,
+              "vit_adamw_ema: bad arguments");
+  VIT_REQUIRE(ema_weight > 0.f && ema_weight < 1.f, "vit_adamw_ema: ema_weight must lie in (0, 1) (got %g)",
+              (double)ema_weight);
+  const float step_size = lr / bias_corr1;
+  const float inv_sqrt_bc2 = 1.0f / sqrtf(bias_corr2);
+  hipStream_t s = VIT_STREAM(stream);
+  if (shadow_dtype == VIT_BF16)
+    adamw_ema_kernel<bf16_t><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, ema_dev, lr, beta1, beta2, eps, weight_decay,
+                                                               step_size, inv_sqrt_bc2, grad_scale, ema_weight, clip);
+  else
+    adamw_ema_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, ema_dev, lr, beta1, beta2, eps, weight_decay,
+                                                              step_size, inv_sqrt_bc2, grad_scale, ema_weight, clip);
+  return vit::check_launch("vit_adamw_ema");
+}
+
+extern "C" int vit_ema_swap(const vit_tensor_chunk* table_dev, float* const* ema_dev, int64_t nchunks,
+                            int32_t shadow_dtype, void* stream) {
+  VIT_REQUIRE(table_dev && ema_dev && nchunks > 0, "vit_ema_swap: bad arguments");
+  hipStream_t s = VIT_STREAM(stream);
+  if (shadow_dtype == VIT_BF16) ema_swap_kernel<bf16_t><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, ema_dev);
+  else ema_swap_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, ema_dev);
+  return vit::check_launch("vit_ema_swap");
 }
 
 extern "C" int vit_pack(const vit_tensor_chunk* table_dev, int64_t nchunks, int32_t shadow_dtype, void* stream) {

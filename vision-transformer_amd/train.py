@@ -20,6 +20,7 @@ as one kernel per batch (VisionTransformer/data.py, bit-exact with Pillow), on t
 tensorboard is used when importable, else scalars go to a JSONL file.
 """
 import argparse
+import contextlib
 import glob
 import json
 import os
@@ -192,7 +193,7 @@ def _rank_world():
 
 
 def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkpoint_dir, lr=1e-4,
-          log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None):
+          log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None, ema_decay=None):
     """The reference training loop (train.py:60-119) on the HIP path.  Returns the last epoch's summed loss.
 
     Defaults keep the GPU busy: no host sync inside the epoch — the epoch loss is summed on the device and the per-step
@@ -207,13 +208,18 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     `max_grad_norm` (not in the reference, whose loop has no clipping, train.py:94-96): clip by global gradient norm
     inside the optimizer step (optim.make_optimizer).  "GradNorm/train_batch" — the norm before clipping — is then
     logged at the loss's cadence and, like it, stays on the device until the epoch ends (`reference_loop`: per step,
-    with its sync); rank 0 prints how many steps the epoch skipped for a non-finite norm."""
+    with its sync); rank 0 prints how many steps the epoch skipped for a non-finite norm.
+
+    `ema_decay` (not in the reference either): the optimizer keeps an exponential moving average of the weights inside
+    its step (optim.make_optimizer), validation scores the EMA weights (swapped in for `evaluate` and out again), and
+    the checkpoint dict gains one key, "ema_state_dict" — the model's state_dict with the EMA in place of every trained
+    parameter.  Resuming needs nothing more: the EMA is part of "optimizer_state_dict"."""
     rank, world = _rank_world()
     saved_epoch = search_checkpoint(checkpoint_dir)
     torch.manual_seed(0)                              # identical init on every rank
     model = vit.VisionTransformer(configs)
     optimizer = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=device,
-                               max_grad_norm=max_grad_norm)
+                               max_grad_norm=max_grad_norm, ema_decay=ema_decay)
     iteration = 0
     if saved_epoch is not None:
         print(f"Checkpoint Found. Loading model from epoch {saved_epoch}")
@@ -221,7 +227,7 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
         model.load_state_dict(ckpt["model_state_dict"])
         model = model.to(device)
         optimizer = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=device,
-                                   max_grad_norm=max_grad_norm)
+                                   max_grad_norm=max_grad_norm, ema_decay=ema_decay)
         optimizer.load_state_dict(ckpt["optimizer_state_dict"])
         iteration = 0 if reference_loop else int(ckpt.get("step", 0))
     else:
@@ -283,14 +289,17 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
         acc = None
         if test_loader is not None and (reference_loop or (eval_iter and epoch % eval_iter == 0)):
             from sklearn.metrics import accuracy_score
-            acc = round(float(evaluate(model, test_loader, accuracy_score)), 2)
+            with optimizer.ema_weights() if ema_decay is not None else contextlib.nullcontext():
+                acc = round(float(evaluate(model, test_loader, accuracy_score)), 2)
             if writer is not None:
                 writer.add_scalar("val?acc", acc, epoch)
         if rank == 0:
             os.makedirs(checkpoint_dir, exist_ok=True)
-            torch.save({"epoch": epoch, "model_state_dict": model.state_dict(),
-                        "optimizer_state_dict": optimizer.state_dict(), "loss": running_loss, "step": iteration},
-                       os.path.join(checkpoint_dir, f"{epoch}.pt"))
+            ckpt = {"epoch": epoch, "model_state_dict": model.state_dict(),
+                    "optimizer_state_dict": optimizer.state_dict(), "loss": running_loss, "step": iteration}
+            if ema_decay is not None:
+                ckpt["ema_state_dict"] = optimizer.ema_state_dict(model)
+            torch.save(ckpt, os.path.join(checkpoint_dir, f"{epoch}.pt"))
             ips = nb * configs.batch_size * world / max(dt, 1e-9)
             print(f"Epoch {epoch}, curr loss: {running_loss:.4f}, mean_accuracy: {acc}, "
                   f"{nb} steps in {dt:.2f}s ({ips:.1f} img/s over {world} GPU(s))", flush=True)
@@ -302,15 +311,16 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     return running_loss
 
 
-def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None):
+def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None, ema_decay=None):
     """The hot loop body (train.py:91-98: forward, CE loss, zero_grad(set_to_none), backward, AdamW step) on one
     synthetic batch already resident on `dev`, dropout on; returns (seconds per timed step, last loss).  This is the
     repo's own CPU training step that bench.py's `cpu_baseline` times (BASELINE config 1).  Unclipped unless
-    `max_grad_norm` is given."""
+    `max_grad_norm` is given, and without a weight EMA unless `ema_decay` is."""
     dev = torch.device(dev or device)
     torch.manual_seed(0)
     model = vit.VisionTransformer(configs).to(dev).train()
-    opt = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=dev, max_grad_norm=max_grad_norm)
+    opt = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=dev, max_grad_norm=max_grad_norm,
+                         ema_decay=ema_decay)
     g = torch.Generator().manual_seed(seed)
     n_img = int(round((configs.num_patches ** 0.5) * configs.patch_size))
     x = torch.randn(configs.batch_size, configs.input_channels, n_img, n_img, generator=g).to(dev)
@@ -347,6 +357,9 @@ def main():
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="FLOAT",
                     help="clip gradients to this global L2 norm inside the optimizer step and log GradNorm/train_batch "
                          "(default: no clipping, as the reference)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
+                    help="keep an exponential moving average of the weights with this decay inside the optimizer "
+                         "step, validate on it and save it as ema_state_dict (default: none, as the reference)")
     ap.add_argument("--reference-loop", action="store_true",
                     help="the reference's loop bookkeeping exactly: validate every epoch, restart the step counter on "
                          "resume, host-summed loss (train.py:60-119)")
@@ -386,7 +399,8 @@ def main():
                            batch_size=args.batch, device="cpu")
     if args.bench:
         steps = args.steps or 30
-        sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm)
+        sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm,
+                               ema_decay=args.ema_decay)
         print(json.dumps({"device": device, "model": args.model, "img": args.img, "batch": args.batch,
                           "dtype": args.dtype, "threads": torch.get_num_threads(), "warmup": args.warmup,
                           "steps": steps, "ms_per_step": round(sec * 1e3, 3),
@@ -428,7 +442,8 @@ def main():
         test_loader = torch.utils.data.DataLoader(test_set, batch_size=args.batch, num_workers=args.workers,
                                                   sampler=tsampler, drop_last=False, pin_memory=pin)
     train(cfg, train_loader, test_loader, args.epochs, args.eval_iter, args.log_dir, args.checkpoint_dir,
-          lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop, max_grad_norm=args.clip_grad_norm)
+          lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop, max_grad_norm=args.clip_grad_norm,
+          ema_decay=args.ema_decay)
     if world > 1:
         dist.destroy_process_group()
 
