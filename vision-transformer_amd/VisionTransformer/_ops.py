@@ -376,21 +376,26 @@ def pack(table_dev, nchunks, shadow_dtype, stream=None):
 CHUNK = int(os.environ.get("VIT_ADAMW_CHUNK", 8192))
 
 
+def _chunks(numel):
+    """The (offset, n) pieces a tensor of `numel` elements is cut into: the one place that knows the boundaries, so
+    the chunk table and the EMA pointer array that goes with it cannot disagree.  Reads CHUNK at call time."""
+    return [(off, min(CHUNK, numel - off)) for off in range(0, numel, CHUNK)]
+
+
 def build_chunk_table(entries, device):
     """entries: list of (p, g, m, v, shadow) tensors (fp32 contiguous, shadow may be None).  Returns (uint8 device
     tensor holding the vit_tensor_chunk array, nchunks)."""
     chunks = []
     for p, g, m, v, sh in entries:
-        n = p.numel()
         es = sh.element_size() if sh is not None else 0
-        for off in range(0, n, CHUNK):
+        for off, n in _chunks(p.numel()):
             c = _lib.TensorChunk()
             c.p = p.data_ptr() + 4 * off
             c.g = (g.data_ptr() + 4 * off) if g is not None else 0
             c.m = (m.data_ptr() + 4 * off) if m is not None else 0
             c.v = (v.data_ptr() + 4 * off) if v is not None else 0
             c.shadow = (sh.data_ptr() + es * off) if sh is not None else None
-            c.n = min(CHUNK, n - off)
+            c.n = n
             chunks.append(c)
     arr = (_lib.TensorChunk * len(chunks))(*chunks)
     host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
@@ -399,17 +404,15 @@ def build_chunk_table(entries, device):
 
 def build_ema_pointers(entries, device):
     """The EMA pointer array that goes with build_chunk_table(entries): `entries` is a list of (p, ema) in the same
-    order, ema an fp32 contiguous tensor of p's size (4-B alignment suffices) or None.  One pointer per chunk, cut at
-    the same CHUNK boundaries; 0 (NULL) for every chunk of a tensor without an EMA.  Returns (int64 device tensor,
-    nchunks)."""
+    order, ema an fp32 contiguous tensor of p's size (4-B alignment suffices) or None.  One pointer per chunk, cut by
+    the same _chunks(); 0 (NULL) for every chunk of a tensor without an EMA.  Returns (int64 device tensor, nchunks)."""
     ptrs = []
     for p, e in entries:
         n = p.numel()
         if e is not None and (e.dtype != torch.float32 or e.numel() != n or not e.is_contiguous()
                               or e.device != p.device):
             raise ValueError("an EMA tensor must be contiguous float32 of its parameter's size, on its device")
-        for off in range(0, n, CHUNK):
-            ptrs.append(e.data_ptr() + 4 * off if e is not None else 0)
+        ptrs.extend(e.data_ptr() + 4 * off if e is not None else 0 for off, _ in _chunks(n))
     return torch.tensor(ptrs, dtype=torch.int64).to(device), len(ptrs)
 
 

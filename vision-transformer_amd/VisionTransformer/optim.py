@@ -8,6 +8,7 @@ interchangeable with the reference's (train.py:73,110).
 
 CrossEntropyLoss: nn.CrossEntropyLoss() (mean) as one fused softmax + NLL + gradient kernel.
 """
+import collections
 import contextlib
 import math
 
@@ -56,11 +57,108 @@ class _EmaSurface:
         return out
 
 
+def _closure_loss(closure):
+    if closure is None:
+        return None
+    with torch.enable_grad():
+        return closure()
+
+
+class _StepTable:
+    """One cached launch of the fused step: the device chunk table over the parameters `params` (and, where any of
+    them has an EMA, the EMA pointer array cut alike), with what valid() compares to tell that it still describes
+    them.  `keep` holds every tensor whose pointer the device table carries."""
+
+    __slots__ = ("version", "params", "grads", "grad_ptrs", "param_ptrs", "moments", "emas", "dev_tab", "ema_dev",
+                 "nchunks", "shadow_dtype", "device", "keep")
+
+    @classmethod
+    def build(cls, opt, ps):
+        state, tab = opt.state, cls()
+        shadows = [shadow_of(p) for p in ps]
+        # one shadow dtype per table, the first there is: the kernel writes no shadow of another
+        tab.shadow_dtype = sdt = next((s.dtype for s in shadows if s is not None), torch.float32)
+        tab.version, tab.params, tab.device = opt._version, list(ps), ps[0].device
+        tab.grads = [p.grad for p in ps]
+        tab.moments = [(state[p]["exp_avg"], state[p]["exp_avg_sq"]) for p in ps]
+        tab.keep = [(p, g, m, v, s if (s is not None and s.dtype == sdt) else None)
+                    for p, g, (m, v), s in zip(ps, tab.grads, tab.moments, shadows)]
+        if not all(t.is_contiguous() for _, g, m, v, _ in tab.keep for t in (g, m, v)):
+            raise RuntimeError("FusedAdamW: non-contiguous grad/state")
+        tab.dev_tab, tab.nchunks = _ops.build_chunk_table(tab.keep, tab.device)
+        tab.emas, tab.ema_dev = [state[p].get("ema") for p in ps], None
+        if all(e is None for e in tab.emas):
+            tab.emas = None
+        else:
+            tab.ema_dev, _ = _ops.build_ema_pointers(list(zip(ps, tab.emas)), tab.device)
+        tab.param_ptrs, tab.grad_ptrs = [p.data_ptr() for p in ps], [g.data_ptr() for g in tab.grads]
+        return tab
+
+    def valid(self, opt, ps):
+        """Same optimizer version, same parameters, every parameter still holds the same .grad tensor object and the
+        same moment tensor objects as when the table was built, and no parameter's or gradient's storage moved (`p.data = ...`
+        re-points storage without changing any object identity; ADVICE r3).  Two data_ptr() per parameter plus
+        identity checks: this runs every step.  The engine's shadows change only when it rebuilds its buffers, and
+        then every gradient view is a new object too.  A table built with EMA pointers also wants every parameter's
+        `state[p]["ema"]` to be the tensor object it points at; one built without serves only the EMA-less step."""
+        if self.version != opt._version or len(self.params) != len(ps):
+            return False
+        state = opt.state
+        if self.emas is None:      # a table without EMA pointers serves only the EMA-less step (no per-parameter work)
+            if opt.ema_decay is not None:
+                return False
+        elif any(state[a].get("ema") is not e for a, e in zip(self.params, self.emas)):
+            return False
+        for a, b, g, ptr, (m, v), gp in zip(self.params, ps, self.grads, self.param_ptrs, self.moments,
+                                            self.grad_ptrs):
+            # the gradient's storage too: `p.grad.data = t` / `p.grad.set_(...)` keep the .grad object (ADVICE r5)
+            if a is not b or a.grad is not g or a.data_ptr() != ptr or g.data_ptr() != gp:
+                return False
+            st = state[a]
+            if st["exp_avg"] is not m or st["exp_avg_sq"] is not v:
+                return False
+        return True
+
+
+_SwapKey = collections.namedtuple("_SwapKey", "param ptr ema shadow")      # what a parameter's swap entry was cut from
+_SwapTable = collections.namedtuple("_SwapTable", "dev_tab ema_dev nchunks shadow_dtype keep")
+
+
+class _SwapTables:
+    """swap_ema()'s launches: every parameter that has an EMA exactly once, one table per (device, shadow dtype), in
+    practice one.  Valid while the optimizer's version and every parameter's storage, EMA tensor object and shadow
+    object are those it was built from."""
+
+    __slots__ = ("version", "keys", "tables")
+
+    def __init__(self, opt, ps):
+        self.version = opt._version
+        self.keys = [_SwapKey(p, p.data_ptr(), opt.state[p]["ema"], shadow_of(p)) for p in ps]
+        groups = {}
+        for k in self.keys:
+            groups.setdefault((k.param.device, k.shadow.dtype if k.shadow is not None else None), []).append(k)
+        for dev in {d for d, _ in groups}:      # shadow-less parameters ride in their device's first table
+            bare = groups.pop((dev, None), None)
+            if bare:
+                key = next(((d, s) for d, s in groups if d == dev), (dev, torch.float32))
+                groups.setdefault(key, []).extend(bare)
+        self.tables = []
+        for (dev, sdt), keys in groups.items():
+            dev_tab, n = _ops.build_chunk_table([(k.param.detach(), None, None, None, k.shadow) for k in keys], dev)
+            ema_dev, _ = _ops.build_ema_pointers([(k.param, k.ema) for k in keys], dev)
+            self.tables.append(_SwapTable(dev_tab, ema_dev, n, sdt, keys))
+
+    def valid(self, opt, ps):
+        return self.version == opt._version and len(self.keys) == len(ps) and all(
+            k.param is p and p.data_ptr() == k.ptr and opt.state[p]["ema"] is k.ema and shadow_of(p) is k.shadow
+            for k, p in zip(self.keys, ps))
+
+
 class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
     """Step bookkeeping stays on the host: each group's per-parameter 'step' entries are 0-d views of ONE CPU
     tensor (torch AdamW's state format, so `state_dict()` / `load_state_dict()` interchange with it), advanced by a
     single in-place add per step, with a host-side mirror of the counts for the bias corrections — no per-parameter
-    `.item()` or `+= 1` on the step path.  Device chunk tables are cached per (group, step-count class) and hold
+    `.item()` or `+= 1` on the step path.  Device chunk tables (_StepTable) are cached per (group, step count) and hold
     references to every tensor whose pointer they carry.  A cached table is reused while the optimizer's version
     (bumped by load_state_dict / add_param_group / fresh state) is unchanged and every parameter still has the very
     same .grad tensor object, the same moment tensor objects and every parameter the storage it was tabled with, so
@@ -146,29 +244,31 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
         table — all on the current stream, which the engine's backward() has already made wait for the weight-
         gradient stream and the all-reduce handles."""
         _check_max_grad_norm(self.max_grad_norm)
-        device = work[0][5]
-        if any(w[5] != device for w in work):
+        device = next(tab.device for tab, _, _ in work)
+        if any(tab.device != device for tab, _, _ in work):
             raise RuntimeError("FusedAdamW: a global gradient norm needs every parameter on one device")
-        total = sum(w[1] for w in work)
+        total = sum(tab.nchunks for tab, _, _ in work)
         if self._partial is None or self._partial.device != device or self._partial.numel() < total:
             self._partial = torch.empty(total, dtype=torch.float64, device=device)
         clip = self._clip_state(device)
         off = 0
-        for dev_tab, n, *_ in work:
-            _ops.grad_sumsq(dev_tab, n, self.grad_scale, self._partial[off:off + n])
-            off += n
+        for tab, _, _ in work:
+            _ops.grad_sumsq(tab.dev_tab, tab.nchunks, self.grad_scale, self._partial[off:off + tab.nchunks])
+            off += tab.nchunks
         _ops.grad_clip_finish(self._partial, total, self.max_grad_norm, clip, self.skip_nonfinite)
-        for dev_tab, n, sdt, group, t, _, ema_dev in work:
-            self._adamw(dev_tab, n, sdt, group, t, clip, ema_dev)
+        for tab, group, t in work:
+            self._adamw(tab, group, t, clip)
 
-    def _adamw(self, dev_tab, n, sdt, group, t, clip=None, ema_dev=None):
+    def _adamw(self, tab, group, t, clip=None):
+        """The update of one table's parameters, all at step count `t`."""
         b1, b2 = group["betas"]
         if self.ema_decay is not None:
-            _ops.adamw_ema(dev_tab, ema_dev, n, group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                           1.0 - b1 ** t, 1.0 - b2 ** t, self.grad_scale, sdt, self.ema_decay, clip=clip)
+            _ops.adamw_ema(tab.dev_tab, tab.ema_dev, tab.nchunks, group["lr"], b1, b2, group["eps"],
+                           group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t, self.grad_scale, tab.shadow_dtype,
+                           self.ema_decay, clip=clip)
             return
-        _ops.adamw(dev_tab, n, group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t,
-                   1.0 - b2 ** t, self.grad_scale, sdt, clip=clip)
+        _ops.adamw(tab.dev_tab, tab.nchunks, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                   1.0 - b1 ** t, 1.0 - b2 ** t, self.grad_scale, tab.shadow_dtype, clip=clip)
 
     # ---- step counters ------------------------------------------------------------------------------------------
     def _step_state(self, gi, group):
@@ -193,152 +293,94 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
         if hasattr(self, "_tables"):
             self.invalidate()
 
+    def _make_state(self, plist, ema):
+        """Moments, and with `ema` an EMA, for every parameter of `plist` that has none yet.  True if any was made."""
+        fresh = False
+        for p in plist:
+            if not p.is_cuda or p.dtype != torch.float32 or p.grad.dtype != torch.float32:
+                raise RuntimeError("FusedAdamW: parameters and grads must be float32 on a ROCm device")
+            if p.grad.is_sparse:
+                raise RuntimeError("FusedAdamW does not support sparse gradients")
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                fresh = True
+            if ema and "ema" not in st:      # with the moments, or at the first step after a torch checkpoint
+                st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
+                fresh = True
+        return fresh
+
+    def _advance(self, gi, group, idx):
+        """One in-place add on the shared tensor, the host mirror in Python ints.  Returns {step count: [params]}."""
+        ps_all = group["params"]
+        buf, host = self._step_state(gi, group)
+        if len(idx) == len(ps_all):
+            buf += 1
+        else:
+            buf[torch.tensor(idx)] += 1
+        by_step = {}
+        for i in idx:
+            host[i] += 1
+            by_step.setdefault(host[i], []).append(ps_all[i])
+        return by_step
+
+    def _table(self, key, ps):
+        """The cached table under `key` while it still describes `ps` (_StepTable.valid), else a new one in its place"""
+        tab = self._tables.get(key)
+        if tab is None or not tab.valid(self, ps):
+            tab = self._tables[key] = _StepTable.build(self, ps)
+        return tab
+
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = _closure_loss(closure)
         self._refuse_step_while_swapped()
-        ema = self.ema_decay is not None
-        if ema:
-            _check_ema_decay(self.ema_decay)
-        clipped, work = self.max_grad_norm is not None, []
+        _check_ema_decay(self.ema_decay)
+        ema, clipped, work = self.ema_decay is not None, self.max_grad_norm is not None, []
         for gi, group in enumerate(self.param_groups):
             ps_all = group["params"]
             idx = [i for i, p in enumerate(ps_all) if p.grad is not None]
             if not idx:
                 continue
-            plist = [ps_all[i] for i in idx]
-            fresh = False
-            for p in plist:
-                if not p.is_cuda or p.dtype != torch.float32 or p.grad.dtype != torch.float32:
-                    raise RuntimeError("FusedAdamW: parameters and grads must be float32 on a ROCm device")
-                if p.grad.is_sparse:
-                    raise RuntimeError("FusedAdamW does not support sparse gradients")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    fresh = True
-                if ema and "ema" not in st:      # with the moments, or at the first step after a torch checkpoint
-                    st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
-                    fresh = True
-            if fresh:
+            if self._make_state([ps_all[i] for i in idx], ema):
                 self.invalidate()
-            buf, host = self._step_state(gi, group)
-            # advance the counters: one in-place add on the shared tensor, host mirror in Python ints
-            if len(idx) == len(ps_all):
-                buf += 1
-            else:
-                buf[torch.tensor(idx)] += 1
-            by_step = {}
-            for i in idx:
-                host[i] += 1
-                by_step.setdefault(host[i], []).append(ps_all[i])
+            by_step = self._advance(gi, group, idx)
             for t, ps in by_step.items():
                 # one table for the whole group while every parameter has the same step count, else one per count
-                key = (gi, "all") if len(by_step) == 1 else (gi, "t", t)
-                tab = self._tables.get(key)
-                if tab is not None and not self._table_valid(tab, ps):
-                    tab = None
-                if tab is None:
-                    shadows = [shadow_of(p) for p in ps]
-                    sdt = next((s.dtype for s in shadows if s is not None), torch.float32)
-                    shadows = [s if (s is not None and s.dtype == sdt) else None for s in shadows]
-                    entries = [(p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"], s)
-                               for p, s in zip(ps, shadows)]
-                    for p, g, m, v, _ in entries:
-                        for tt in (g, m, v):
-                            if not tt.is_contiguous():
-                                raise RuntimeError("FusedAdamW: non-contiguous grad/state")
-                    dev_tab, n = _ops.build_chunk_table(entries, ps[0].device)
-                    emas = [self.state[p].get("ema") for p in ps]
-                    if all(e is None for e in emas):
-                        emas = ema_dev = None
-                    else:
-                        ema_dev, _ = _ops.build_ema_pointers(list(zip(ps, emas)), ps[0].device)
-                    # entries keep every tabled tensor alive; the raw shadow list is what the identity check compares
-                    tab = (self._version, list(ps), [p.grad for p in ps], [shadow_of(p) for p in ps], dev_tab, n,
-                           sdt, entries, [p.data_ptr() for p in ps],
-                           [(self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in ps],
-                           [p.grad.data_ptr() for p in ps], emas, ema_dev)
-                    self._tables[key] = tab
-                dev_tab, n, sdt, ema_dev = tab[4], tab[5], tab[6], tab[12]
+                tab = self._table((gi, "all") if len(by_step) == 1 else (gi, "t", t), ps)
                 if clipped:      # the norm spans every table: launch once they all exist
-                    work.append((dev_tab, n, sdt, group, t, ps[0].device, ema_dev))
+                    work.append((tab, group, t))
                 else:
-                    self._adamw(dev_tab, n, sdt, group, t, None, ema_dev)
+                    self._adamw(tab, group, t)
         if work:
             self._clipped_launch(work)
         return loss
 
-    def _table_valid(self, tab, ps):
-        """Same optimizer version, same parameters, every parameter still holds the same .grad tensor object and the
-        same moment tensor objects as when the table was built, and no parameter's or gradient's storage moved (`p.data = ...`
-        re-points storage without changing any object identity; ADVICE r3).  Two data_ptr() per parameter plus
-        identity checks: this runs every step.  The engine's shadows change only when it rebuilds its buffers, and
-        then every gradient view is a new object too.  A table built with EMA pointers also wants every parameter's
-        `state[p]["ema"]` to be the tensor object it points at; one built without serves only the EMA-less step."""
-        ver, tps, grads, ptrs, moments, gptrs = tab[0], tab[1], tab[2], tab[8], tab[9], tab[10]
-        if ver != self._version or len(tps) != len(ps):
-            return False
-        emas = tab[11]
-        if emas is None:      # a table without EMA pointers serves only the EMA-less step (no per-parameter work)
-            if self.ema_decay is not None:
-                return False
-        elif any(self.state[a].get("ema") is not e for a, e in zip(tps, emas)):
-            return False
-        state = self.state
-        for a, b, g, ptr, (m, v), gp in zip(tps, ps, grads, ptrs, moments, gptrs):
-            # the gradient's storage too: `p.grad.data = t` / `p.grad.set_(...)` keep the .grad object (ADVICE r5)
-            if a is not b or a.grad is not g or a.data_ptr() != ptr or g.data_ptr() != gp:
-                return False
-            st = state[a]
-            if st["exp_avg"] is not m or st["exp_avg_sq"] is not v:
-                return False
-        return True
-
     # ---- weight EMA ---------------------------------------------------------------------------------------------
-    def _ema_swap_tables(self):
-        """Chunk tables for vit_ema_swap: every parameter that has an EMA exactly once, whichever step tables exist
-        (those carry gradient pointers, go stale with zero_grad(set_to_none=True), and two of them may hold the same
-        parameter).  One table per (device, shadow dtype), in practice one.  Reused while the optimizer's version, every
-        parameter's storage, EMA tensor object and shadow object are those it was built from."""
+    def _ema_params(self):
         state = self.state       # .get: looking must not create an (empty) state entry for a parameter that has none
-        ps = [p for g in self.param_groups for p in g["params"] if (state.get(p) or {}).get("ema") is not None]
+        return [p for g in self.param_groups for p in g["params"] if (state.get(p) or {}).get("ema") is not None]
+
+    def _ema_swap_tables(self):
+        """Chunk tables for vit_ema_swap, of their own whichever step tables exist: those carry gradient pointers, go
+        stale with zero_grad(set_to_none=True), and two of them may hold the same parameter."""
+        ps = self._ema_params()
         cached = self._swap_tables
-        if cached is not None and cached[0] == self._version and len(cached[1]) == len(ps) and all(
-                a is b and a.data_ptr() == ptr and self.state[a]["ema"] is e and shadow_of(a) is s
-                for (a, ptr, e, s), b in zip(cached[1], ps)):
-            return cached[2]
-        groups = {}
-        for p in ps:
-            s = shadow_of(p)
-            groups.setdefault((p.device, s.dtype if s is not None else None), []).append((p, self.state[p]["ema"], s))
-        for dev in {d for d, _ in groups}:      # shadow-less parameters ride in their device's first table
-            bare = groups.pop((dev, None), None)
-            if bare:
-                key = next((k for k in groups if k[0] == dev), (dev, torch.float32))
-                groups.setdefault(key, []).extend(bare)
-        tables = []
-        for (dev, sdt), ents in groups.items():
-            if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p, _, _ in ents):
+        if cached is None or not cached.valid(self, ps):
+            if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in ps):
                 raise RuntimeError("FusedAdamW: parameters must be contiguous float32 on a ROCm device")
-            dev_tab, n = _ops.build_chunk_table([(p.detach(), None, None, None, s) for p, _, s in ents], dev)
-            ema_dev, _ = _ops.build_ema_pointers([(p, e) for p, e, _ in ents], dev)
-            tables.append((dev_tab, ema_dev, n, sdt, ents))
-        self._swap_tables = (self._version, [(p, p.data_ptr(), self.state[p]["ema"], shadow_of(p)) for p in ps], tables)
-        return tables
+            cached = self._swap_tables = _SwapTables(self, ps)
+        return cached.tables
 
     @torch.no_grad()
     def swap_ema(self):
         """Exchange every parameter that has an EMA with it, in place, and refresh its compute-dtype shadow from the
         new value: one launch per table, no repack, no engine rebuild (the engine reads the same buffers).  A second
         call restores every bit.  Parameters without an EMA are left alone."""
-        for dev_tab, ema_dev, n, sdt, _ in self._ema_swap_tables():
-            _ops.ema_swap(dev_tab, ema_dev, n, sdt)
+        for tab in self._ema_swap_tables():
+            _ops.ema_swap(tab.dev_tab, tab.ema_dev, tab.nchunks, tab.shadow_dtype)
         self._ema_swapped = not self._ema_swapped
 
 
@@ -368,7 +410,31 @@ def _check_max_grad_norm(max_grad_norm):
         raise ValueError(f"max_grad_norm must be None or a positive finite number (got {max_grad_norm!r})")
 
 
-class ClippedAdamW(torch.optim.AdamW):
+class _HostClip:
+    """What the host path's ClippedAdamW and EmaAdamW share: clip_grad_norm_ before the step, the skip of a step
+    whose norm is not finite, and the norm and skip count that grad_norm() / skipped_steps() report."""
+
+    def _init_clip(self, max_grad_norm, skip_nonfinite):
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
+        self._norm = torch.zeros(())
+        self._skipped = 0
+
+    def _clip_grads(self, params):
+        """Clip the gradients of `params` in place.  True when the step is to be skipped for a non-finite norm."""
+        self._norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm).detach().clone()
+        skip = self.skip_nonfinite and not bool(torch.isfinite(self._norm))
+        self._skipped += skip
+        return skip
+
+    def grad_norm(self):
+        return self._norm.clone()
+
+    def skipped_steps(self):
+        return torch.tensor(float(self._skipped))
+
+
+class ClippedAdamW(_HostClip, torch.optim.AdamW):
     """The host path's counterpart of FusedAdamW(max_grad_norm=...): torch.optim.AdamW whose step() first runs
     torch.nn.utils.clip_grad_norm_ over every parameter with a gradient, and with `skip_nonfinite` leaves parameters
     and state alone when that norm is inf or NaN (the gradients are still scaled by the non-finite step's
@@ -380,34 +446,17 @@ class ClippedAdamW(torch.optim.AdamW):
         if max_grad_norm is None:
             raise ValueError("ClippedAdamW needs a max_grad_norm; use torch.optim.AdamW to train unclipped")
         super().__init__(params, **kwargs)
-        self.max_grad_norm = max_grad_norm
-        self.skip_nonfinite = skip_nonfinite
-        self._norm = torch.zeros(())
-        self._skipped = 0
+        self._init_clip(max_grad_norm, skip_nonfinite)
 
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = _closure_loss(closure)
         params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
-        if not params:
-            return loss
-        self._norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm).detach().clone()
-        if self.skip_nonfinite and not bool(torch.isfinite(self._norm)):
-            self._skipped += 1
-            return loss
-        super().step()
+        if params and not self._clip_grads(params):
+            super().step()
         return loss
 
-    def grad_norm(self):
-        return self._norm.clone()
 
-    def skipped_steps(self):
-        return torch.tensor(float(self._skipped))
-
-
-class EmaAdamW(_EmaSurface, torch.optim.AdamW):
+class EmaAdamW(_EmaSurface, _HostClip, torch.optim.AdamW):
     """The host path's counterpart of FusedAdamW(ema_decay=...), in torch ops: torch.optim.AdamW whose step() then
     moves `state[p]["ema"]` by ema += (1 - ema_decay) * (p_new - ema) for every parameter it stepped.  Same
     initialisation (a clone of the weights before the parameter's first update here), same surface (`ema_decay`
@@ -421,26 +470,15 @@ class EmaAdamW(_EmaSurface, torch.optim.AdamW):
             raise ValueError("EmaAdamW needs an ema_decay; use torch.optim.AdamW or ClippedAdamW to train without")
         super().__init__(params, **kwargs)
         self.ema_decay = ema_decay
-        self.max_grad_norm = max_grad_norm
-        self.skip_nonfinite = skip_nonfinite
-        self._norm = torch.zeros(())
-        self._skipped = 0
+        self._init_clip(max_grad_norm, skip_nonfinite)
 
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = _closure_loss(closure)
         self._refuse_step_while_swapped()
         _check_ema_decay(self.ema_decay)
         params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
-        if not params:
+        if not params or (self.max_grad_norm is not None and self._clip_grads(params)):
             return loss
-        if self.max_grad_norm is not None:
-            self._norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm).detach().clone()
-            if self.skip_nonfinite and not bool(torch.isfinite(self._norm)):
-                self._skipped += 1
-                return loss
         # torch's step() creates its state only where there is none at all, so a new EMA joins the state after it
         new = [(p, p.detach().clone(memory_format=torch.contiguous_format)) for p in params
                if "ema" not in self.state.get(p, ())]
@@ -464,12 +502,6 @@ class EmaAdamW(_EmaSurface, torch.optim.AdamW):
                     p.copy_(e)
                     e.copy_(old)
         self._ema_swapped = not self._ema_swapped
-
-    def grad_norm(self):
-        return self._norm.clone()
-
-    def skipped_steps(self):
-        return torch.tensor(float(self._skipped))
 
 
 def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda", max_grad_norm=None, skip_nonfinite=True,

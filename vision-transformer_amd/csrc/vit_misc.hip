@@ -735,19 +735,30 @@ extern "C" int vit_softmax_xent(const float* logits, const int64_t* labels, int6
   return vit::check_launch("vit_softmax_xent");
 }
 
+// Host side of the chunk-table launchers.  What the three AdamW entry points check alike, reported under the name
+// `who` of the one that was called (`ptrs`: every pointer it cannot do without is set), and the two factors their
+// kernels take in place of the bias corrections.
+static int adamw_factors(const char* who, bool ptrs, int64_t nchunks, float lr, float bias_corr1, float bias_corr2,
+                         float* step_size, float* inv_sqrt_bc2) {
+  VIT_REQUIRE(ptrs && nchunks > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f, "%s: bad arguments", who);
+  *step_size = lr / bias_corr1;
+  *inv_sqrt_bc2 = 1.0f / sqrtf(bias_corr2);
+  return VIT_OK;
+}
+
+// KERNEL<shadow dtype>, one 256-thread workgroup per chunk of the table: bf16 shadows, or fp32 for any other code.
+// Reads the entry point's own `shadow_dtype`, `nchunks` and `stream`.
+#define TABLE_LAUNCH(KERNEL, ...)                                                                                \
+  if (shadow_dtype == VIT_BF16) KERNEL<bf16_t><<<(unsigned)nchunks, 256, 0, VIT_STREAM(stream)>>>(__VA_ARGS__); \
+  else KERNEL<float><<<(unsigned)nchunks, 256, 0, VIT_STREAM(stream)>>>(__VA_ARGS__)
+
 extern "C" int vit_adamw(const vit_tensor_chunk* table_dev, int64_t nchunks, float lr, float beta1, float beta2,
                          float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
                          int32_t shadow_dtype, void* stream) {
-  VIT_REQUIRE(table_dev && nchunks > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f, "vit_adamw: bad arguments");
-  const float step_size = lr / bias_corr1;
-  const float inv_sqrt_bc2 = 1.0f / sqrtf(bias_corr2);
-  hipStream_t s = VIT_STREAM(stream);
-  if (shadow_dtype == VIT_BF16)
-    adamw_kernel<bf16_t><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, lr, beta1, beta2, eps, weight_decay, step_size,
-                                                           inv_sqrt_bc2, grad_scale);
-  else
-    adamw_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, lr, beta1, beta2, eps, weight_decay, step_size,
-                                                          inv_sqrt_bc2, grad_scale);
+  float step_size, inv_sqrt_bc2;
+  if (int rc = adamw_factors("vit_adamw", table_dev, nchunks, lr, bias_corr1, bias_corr2, &step_size, &inv_sqrt_bc2))
+    return rc;
+  TABLE_LAUNCH(adamw_kernel, table_dev, lr, beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2, grad_scale);
   return vit::check_launch("vit_adamw");
 }
 
@@ -770,17 +781,12 @@ extern "C" int vit_grad_clip_finish(const double* partial, int64_t nparts, float
 extern "C" int vit_adamw_clipped(const vit_tensor_chunk* table_dev, int64_t nchunks, float lr, float beta1,
                                  float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
                                  float grad_scale, int32_t shadow_dtype, const float* clip, void* stream) {
-  VIT_REQUIRE(table_dev && clip && nchunks > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f,
-              "vit_adamw_clipped: bad arguments");
-  const float step_size = lr / bias_corr1;
-  const float inv_sqrt_bc2 = 1.0f / sqrtf(bias_corr2);
-  hipStream_t s = VIT_STREAM(stream);
-  if (shadow_dtype == VIT_BF16)
-    adamw_clipped_kernel<bf16_t><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, lr, beta1, beta2, eps, weight_decay,
-                                                                   step_size, inv_sqrt_bc2, grad_scale, clip);
-  else
-    adamw_clipped_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, lr, beta1, beta2, eps, weight_decay,
-                                                                  step_size, inv_sqrt_bc2, grad_scale, clip);
+  float step_size, inv_sqrt_bc2;
+  if (int rc = adamw_factors("vit_adamw_clipped", table_dev && clip, nchunks, lr, bias_corr1, bias_corr2, &step_size,
+                             &inv_sqrt_bc2))
+    return rc;
+  TABLE_LAUNCH(adamw_clipped_kernel, table_dev, lr, beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2,
+               grad_scale, clip);
   return vit::check_launch("vit_adamw_clipped");
 }
 
@@ -788,35 +794,27 @@ extern "C" int vit_adamw_ema(const vit_tensor_chunk* table_dev, float* const* em
                              float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
                              float bias_corr2, float grad_scale, int32_t shadow_dtype, float ema_weight,
                              const float* clip, void* stream) {
-  VIT_REQUIRE(table_dev && ema_dev && nchunks > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f,
-              "vit_adamw_ema: bad arguments");
+  float step_size, inv_sqrt_bc2;
+  if (int rc = adamw_factors("vit_adamw_ema", table_dev && ema_dev, nchunks, lr, bias_corr1, bias_corr2, &step_size,
+                             &inv_sqrt_bc2))
+    return rc;
   VIT_REQUIRE(ema_weight > 0.f && ema_weight < 1.f, "vit_adamw_ema: ema_weight must lie in (0, 1) (got %g)",
               (double)ema_weight);
-  const float step_size = lr / bias_corr1;
-  const float inv_sqrt_bc2 = 1.0f / sqrtf(bias_corr2);
-  hipStream_t s = VIT_STREAM(stream);
-  if (shadow_dtype == VIT_BF16)
-    adamw_ema_kernel<bf16_t><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, ema_dev, lr, beta1, beta2, eps, weight_decay,
-                                                               step_size, inv_sqrt_bc2, grad_scale, ema_weight, clip);
-  else
-    adamw_ema_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, ema_dev, lr, beta1, beta2, eps, weight_decay,
-                                                              step_size, inv_sqrt_bc2, grad_scale, ema_weight, clip);
+  TABLE_LAUNCH(adamw_ema_kernel, table_dev, ema_dev, lr, beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2,
+               grad_scale, ema_weight, clip);
   return vit::check_launch("vit_adamw_ema");
 }
 
 extern "C" int vit_ema_swap(const vit_tensor_chunk* table_dev, float* const* ema_dev, int64_t nchunks,
                             int32_t shadow_dtype, void* stream) {
   VIT_REQUIRE(table_dev && ema_dev && nchunks > 0, "vit_ema_swap: bad arguments");
-  hipStream_t s = VIT_STREAM(stream);
-  if (shadow_dtype == VIT_BF16) ema_swap_kernel<bf16_t><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, ema_dev);
-  else ema_swap_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev, ema_dev);
+  TABLE_LAUNCH(ema_swap_kernel, table_dev, ema_dev);
   return vit::check_launch("vit_ema_swap");
 }
 
 extern "C" int vit_pack(const vit_tensor_chunk* table_dev, int64_t nchunks, int32_t shadow_dtype, void* stream) {
   VIT_REQUIRE(table_dev && nchunks > 0, "vit_pack: bad arguments");
-  hipStream_t s = VIT_STREAM(stream);
-  if (shadow_dtype == VIT_BF16) pack_kernel<bf16_t><<<(unsigned)nchunks, 256, 0, s>>>(table_dev);
-  else pack_kernel<float><<<(unsigned)nchunks, 256, 0, s>>>(table_dev);
+  TABLE_LAUNCH(pack_kernel, table_dev);
   return vit::check_launch("vit_pack");
 }
+#undef TABLE_LAUNCH
