@@ -561,11 +561,16 @@ VIT_DEV uint32_t v4_epi_row(const EpiParams& e, const GemmArgs& g, int64_t i, in
   return pos;
 }
 
-// The pieces of one half-tile, 2 per wave, by global_load_lds_dwordx4 (per-lane 64-bit source address; the buffer
-// form, buffer_load ... lds, measured 2-4% slower on the k-contiguous-A shapes, neutral on the weight gradients); rows
-// past the operand are clamped to its last row (their products land in output rows / columns that are never stored).
+// The pieces of one half-tile, 2 per wave, by global_load_lds_dwordx4 in its scalar-base form: the source address is
+// a 64-bit SGPR base (the operand pointer plus the k-tile's offset, advanced on the scalar unit) plus a 32-bit per-lane
+// byte offset that depends only on the lane's place in the tile, so it is the same for every k-tile of an item.  (The
+// per-lane 64-bit address form cost one 64-bit VALU add per piece and 2 VGPRs per offset; the buffer form,
+// buffer_load ... lds, measured 2-4% slower on the k-contiguous-A shapes, neutral on the weight gradients.)  The
+// hardware zero-extends the lane offset: it stays below the operand's extent, which the host keeps under 2 GiB, and
+// the k offset (up to the operand's size on the row-strided layouts) is never added into it.  Rows past the operand
+// are clamped to its last row (their products land in output rows / columns that are never stored).
 template <bool KC>
-VIT_DEV void dma_offsets4g(int64_t ld, int64_t rows, int64_t r0, int64_t k0, int wave, int lane, uint32_t (&off)[2]) {
+VIT_DEV void dma_offsets4g(int64_t ld, int64_t rows, int64_t r0, int wave, int lane, uint32_t (&off)[2]) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int ii = wave * 2 + i;
@@ -574,37 +579,36 @@ VIT_DEV void dma_offsets4g(int64_t ld, int64_t rows, int64_t r0, int64_t k0, int
       const int r = ii * 8 + (lane >> 3);
       const int c = (lane & 7) ^ (r & 7);
       gr = min(r0 + r, rows - 1);
-      gk = k0 + c * 8;
+      gk = c * 8;
     } else {
       const int kr = ii * 4 + (lane >> 4);
       const int c = (lane & 15) ^ swz_rs(kr);
-      gk = k0 + kr;
+      gk = kr;
       gr = min(r0 + c * 8, rows - 8);
     }
     off[i] = (uint32_t)((KC ? gr * ld + gk : gk * ld + gr) * 2);
   }
 }
 
+// sbase: the operand at the stage's k-tile (uniform); lds: the LDS byte address of this wave's first piece in the
+// stage's ring slot, an integer computed by scalar adds from the ring's address (no generic -> LDS pointer cast, whose
+// null check was an s_cmp / s_cselect per stage).  The second piece's LDS base goes through a second M0 write.
 // The two pieces are issued as inline asm, not __builtin_amdgcn_global_load_lds: the compiler's waitcnt pass cannot
 // tell an LDS-DMA target from the ds_read_b64_tr_b16 reads of the other ring slots and put `s_waitcnt vmcnt(0)` in
 // front of the transposed-operand reads of every phase (2 per k-tile on the dgrad layout, 3 on the weight-gradient
 // layout), draining the stages the ring keeps in flight.  Completion is ordered explicitly everywhere the slots are
 // read (wait_stage_retired + barrier in the k-loop, vmcnt(0) before the epilogue image and the next item).
-VIT_DEV void dma_half_g(const char* base, const uint32_t (&off)[2], uint32_t soff, bf16_t* half, int wave) {
-  const uint32_t lds = __builtin_amdgcn_readfirstlane(
-      (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(half + wave * 2 * 512));
+VIT_DEV void dma_half_g(const char* sbase, const uint32_t (&off)[2], uint32_t lds) {
   const uint32_t lds1 = lds + 0x400;                  // second piece's LDS base (s_mov only: SCC stays untouched)
-  const char* p0 = base + off[0] + soff;
-  const char* p1 = base + off[1] + soff;
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
   asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off\n\t"
       "s_mov_b32 m0, %3\n\t"
       "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off" ::"v"(p0), "v"(p1), "s"(lds), "s"(lds1)
+      "global_load_lds_dwordx4 %0, %2\n\t"
+      "s_mov_b32 m0, %4\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %2" ::"v"(off[0]), "v"(off[1]), "s"(sbase), "s"(lds), "s"(lds1)
       : "memory", "m0");
 #pragma clang diagnostic pop
 }
@@ -997,12 +1001,12 @@ VIT_DEV void v4_item(const GemmArgs& g, int64_t item, int64_t& tm, int64_t& tn, 
 }
 
 template <bool AKC, bool BKC>
-VIT_DEV void v4_offsets(const GemmArgs& g, int64_t i0, int64_t j0, int64_t k0, int wave, int lane, uint32_t (&oa0)[2],
+VIT_DEV void v4_offsets(const GemmArgs& g, int64_t i0, int64_t j0, int wave, int lane, uint32_t (&oa0)[2],
                         uint32_t (&oa1)[2], uint32_t (&ob0)[2], uint32_t (&ob1)[2]) {
-  dma_offsets4g<AKC>(g.lda, g.M, i0, k0, wave, lane, oa0);
-  dma_offsets4g<AKC>(g.lda, g.M, i0 + 128, k0, wave, lane, oa1);
-  dma_offsets4g<BKC>(g.ldb, g.N, j0, k0, wave, lane, ob0);
-  dma_offsets4g<BKC>(g.ldb, g.N, j0 + 128, k0, wave, lane, ob1);
+  dma_offsets4g<AKC>(g.lda, g.M, i0, wave, lane, oa0);
+  dma_offsets4g<AKC>(g.lda, g.M, i0 + 128, wave, lane, oa1);
+  dma_offsets4g<BKC>(g.ldb, g.N, j0, wave, lane, ob0);
+  dma_offsets4g<BKC>(g.ldb, g.N, j0 + 128, wave, lane, ob1);
 }
 
 // Persistent form (the wide-epilogue kinds: bf16 output, fast epilogue; the host launches one workgroup per CU): a
@@ -1037,25 +1041,29 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
   int64_t i0 = tm * 256, j0 = tn * 256;
   const int64_t nkt = g.K / BK;
   int nk = (int)max((int64_t)0, min(nkt, (sidx + 1) * g.kt_per_split) - sidx * g.kt_per_split);
-  const uint32_t sa = AKC ? BK * 2 : (uint32_t)(BK * g.lda * 2);
-  const uint32_t sb = BKC ? BK * 2 : (uint32_t)(BK * g.ldb * 2);
+  // bytes from one k-tile of an operand to the next; on the row-strided layouts u * sa reaches the operand's size,
+  // so the k offsets live in the 64-bit scalar bases and never in the 32-bit lane offsets
+  const int64_t sa = AKC ? BK * 2 : BK * g.lda * 2;
+  const int64_t sb = BKC ? BK * 2 : BK * g.ldb * 2;
   uint32_t oa0[2], oa1[2], ob0[2], ob1[2];
-  v4_offsets<AKC, BKC>(g, i0, j0, sidx * g.kt_per_split * BK, wave, remat(lane), oa0, oa1, ob0, ob1);
-  const char* pa_ = (const char*)g.a;
-  const char* pb_ = (const char*)g.b;
-#define V4_DMA(P, OFF, SOFF, DST) dma_half_g(P, OFF, SOFF, DST, wave)
+  v4_offsets<AKC, BKC>(g, i0, j0, wave, remat(lane), oa0, oa1, ob0, ob1);
+  // the operands at the item's first k-tile (its K-slice's start)
+  const char* pa_ = (const char*)g.a + sidx * g.kt_per_split * sa;
+  const char* pb_ = (const char*)g.b + sidx * g.kt_per_split * sb;
+  // LDS byte address of this wave's two pieces (2 KiB) in ring slot 0, taken once from the array in address space 3
+  const uint32_t ring_ = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem4 + (uint32_t)wave * 2048u;
 
   // stage s -> (k-tile s>>2, half order A0, B0, B1, A1) in LDS slot s % V4_SLOTS
 #define V4_SLOT(S) (smem4 + ((S) % V4_SLOTS) * HALF)
 #define V4_STAGE(S)                                                                              \
   do {                                                                                           \
     const int s_ = (S), u_ = s_ >> 2;                                                            \
-    bf16_t* slot_ = V4_SLOT(s_);                                                                 \
+    const uint32_t lds_ = ring_ + (uint32_t)(s_ % V4_SLOTS) * (HALF * 2);                        \
     switch (s_ & 3) {                                                                            \
-      case 0: V4_DMA(pa_, oa0, (uint32_t)u_ * sa, slot_); break;                                 \
-      case 1: V4_DMA(pb_, ob0, (uint32_t)u_ * sb, slot_); break;                                 \
-      case 2: V4_DMA(pb_, ob1, (uint32_t)u_ * sb, slot_); break;                                 \
-      default: V4_DMA(pa_, oa1, (uint32_t)u_ * sa, slot_); break;                                \
+      case 0: dma_half_g(pa_ + u_ * sa, oa0, lds_); break;                                       \
+      case 1: dma_half_g(pb_ + u_ * sb, ob0, lds_); break;                                       \
+      case 2: dma_half_g(pb_ + u_ * sb, ob1, lds_); break;                                       \
+      default: dma_half_g(pa_ + u_ * sa, oa1, lds_); break;                                      \
     }                                                                                            \
   } while (0)
 
@@ -1146,7 +1154,9 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
       ni0 = ntm * 256;
       nj0 = ntn * 256;
       nnk = (int)max((int64_t)0, min(nkt, (nsidx + 1) * g.kt_per_split) - nsidx * g.kt_per_split);
-      v4_offsets<AKC, BKC>(g, ni0, nj0, nsidx * g.kt_per_split * BK, wave, remat(lane), oa0, oa1, ob0, ob1);
+      v4_offsets<AKC, BKC>(g, ni0, nj0, wave, remat(lane), oa0, oa1, ob0, ob1);
+      pa_ = (const char*)g.a + nsidx * g.kt_per_split * sa;
+      pb_ = (const char*)g.b + nsidx * g.kt_per_split * sb;
       npre = min(V4_LEAD, 4 * nnk);
       for (int s = 0; s < npre; ++s) V4_STAGE(s);
     }
@@ -1168,6 +1178,15 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
       if (gi.ws) gi.ws += sidx * g.M * g.N;                 // this K-slice's fp32 slab (EPI_SLAB)
       v4_epilogue<TO, KIND, 0>(e, gi, acc, smem4, tid_e, i0, j0, tm);
     }
+    // The next item's stages 0..LEAD-1 went out before the epilogue; its loads and stores are younger, so retiring
+    // stages 0 and 1 waits for them too (vmcnt counts in order): wait for everything.  By the builtin (vmcnt(0)
+    // expcnt(7) lgkmcnt(15)), not inline asm, and on every path out of the epilogue (the exit's blocks statically lead
+    // back to the loop header too), so that the compiler's waitcnt pass sees the epilogue's loads retired: otherwise
+    // it protects the first reuse of one of their destination registers with a vmcnt(0) of its own, which can land
+    // inside the steady k-loop and drain the ring every k-tile (it did, on the bias / residual kinds).  On the last
+    // item it costs nothing: the kernel is not complete before its stores are.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    asm volatile("" ::: "memory");
     if (!have_next) break;
     // advance: the rest of the next item's prologue (its stages 4..LEAD-1 land in slots the image used)
     item = next;
@@ -1177,14 +1196,10 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_v4(GemmArgs g, EpiParams e, 
     nk = nnk;
     nstage = 4 * nk;
     // the offsets again (recomputed rather than kept live across the epilogue: register budget)
-    v4_offsets<AKC, BKC>(g, i0, j0, nsidx * g.kt_per_split * BK, wave, remat(lane), oa0, oa1, ob0, ob1);
-    // stages 0..LEAD-1 went out before the epilogue; its loads and stores are younger, so retiring stages 0 and 1
-    // waits for them too (vmcnt counts in order): wait for everything
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    v4_offsets<AKC, BKC>(g, i0, j0, wave, remat(lane), oa0, oa1, ob0, ob1);
   }
 #undef V4_STAGE
 #undef V4_SLOT
-#undef V4_DMA
 }
 
 // ------------------------------------------------------------------------------------------------------------
