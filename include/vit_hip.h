@@ -73,6 +73,9 @@ const char* vit_last_error(void);
  * ABI 17 adds the gradient-clipping entry points (vit_grad_sumsq, vit_grad_clip_finish, vit_adamw_clipped) and no
  * option name: clipping is an argument of the optimizer, not a kernel variant.
  * ABI 18 adds the weight-EMA entry points (vit_adamw_ema, vit_ema_swap), likewise with no option name.
+ * Since ABI 18, entry points that are purely added do not change the version: a host that needs one checks for the
+ * symbol (dlsym, or a link error).  The version changes only when an existing signature or meaning does.  Added under
+ * 18 this way: vit_softmax_xent_mixed and vit_mix_batch (label smoothing, mixup and CutMix), with no option name.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -262,6 +265,21 @@ int vit_gelu_fwd(const float* x, float* y, int64_t n, void* stream);
 int vit_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream);
 int vit_softmax_xent(const float* logits, const int64_t* labels, int64_t rows, int64_t classes, float* loss,
                      float* dlogits, float* workspace, void* stream);
+/* vit_softmax_xent against a smoothed two-label target (label smoothing, mixup / CutMix labels; the reference's loss,
+ * train.py:81, has neither).  The target of row i is never materialised:
+ *   t_i = (1 - eps) * (lam_i * onehot(a_i) + (1 - lam_i) * onehot(b_i)) + eps / C,   eps = smoothing, C = classes,
+ *   lam_i = 1 (and b_i = a_i) when `lam` or `labels_b` is NULL;
+ *   loss = mean_i( lse_i - (1 - eps) * (lam_i * x[a_i] + (1 - lam_i) * x[b_i]) - (eps / C) * sum_c x[i][c] ),
+ *   dlogits = (softmax - t) / rows.
+ * = F.cross_entropy(logits, labels, label_smoothing=eps) for hard labels, F.cross_entropy(logits, soft_target,
+ * label_smoothing=eps) and timm's SoftTargetCrossEntropy on timm's mixup_target otherwise.  All terms are formed
+ * relative to the row maximum; a_i == b_i and lam in {0, 1} need no special case.  One launch over the rows and the
+ * fixed-order reduce of vit_softmax_xent: no atomics, bitwise repeatable.  workspace: rows floats.  `lam` is DEVICE
+ * memory, [rows].  Refused: a NULL logits / labels_a / loss / dlogits / workspace, rows or classes <= 0, smoothing
+ * outside [0, 1) or NaN, lam without labels_b. */
+int vit_softmax_xent_mixed(const float* logits, const int64_t* labels_a, const int64_t* labels_b /* may be NULL */,
+                           const float* lam /* device, [rows]; may be NULL */, float smoothing, int64_t rows,
+                           int64_t classes, float* loss, float* dlogits, float* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Image pipeline of the training loader (train.py:151-155: convert('RGB') -> transforms.Resize((S, S)) ->
@@ -276,6 +294,31 @@ int vit_resize_ksize(int64_t in_size, int64_t out_size);
 int64_t vit_resize_workspace_bytes(int64_t B, int64_t out_h, int64_t out_w, int64_t ksize);
 int vit_resize_to_tensor(const void* src, const int64_t* meta, int64_t B, int64_t out_h, int64_t out_w, int64_t ksize,
                          void* out, int32_t out_dtype, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Batch mix: mixup and CutMix of a contiguous [B][C][H][W] batch, out of place, in one streaming launch (the
+ * reference has no augmentation beyond its resize, train.py:151-155).  items_dev[i] (DEVICE memory) describes image i:
+ * its partner `src`, its own weight `w` outside the box and the box rows [y0, y1) x columns [x0, x1).  For element
+ * (i, c, y, x):
+ *   inside the box  (y0 <= y < y1 && x0 <= x < x1):  out = x[src_i]                         bitwise
+ *   outside, w_i == 1:                               out = x[i]                             bitwise; x[src_i] is not
+ *                                                    read there, so NaN / inf in it cannot leak
+ *   outside otherwise:                               out = w_i * x[i] + (1 - w_i) * x[src_i]   in fp32, rounded once
+ * mixup: empty box, w = lambda.  CutMix: w = 1, box.  An unmixed image: w = 1, empty box.
+ * 16-byte accesses where x, out and the row length (W * element size) are multiples of 16 bytes, element accesses
+ * otherwise and for a 16-byte unit that a box edge cuts; both forms give the same bits.  Indexing is 64-bit over the
+ * batch (2 GiB and more is fine); one image must have fewer than 2^31 elements.
+ * Refused: a NULL pointer, a non-positive dimension, a dtype other than VIT_F32 / VIT_BF16, `out` overlapping `x`
+ * (image src is read after image i is written).  The table's contents are the caller's contract:
+ * 0 <= src < B, 0 <= w <= 1, 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct vit_mix_item {
+  int32_t src;
+  float w;
+  int32_t y0, y1, x0, x1;
+} vit_mix_item; /* 24 bytes */
+int vit_mix_batch(const void* x, void* out, int32_t dtype /* VIT_F32 | VIT_BF16 */, int64_t B, int64_t C, int64_t H,
+                  int64_t W, const vit_mix_item* items_dev /* [B] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Optimizer (train.py:66,96: torch.optim.AdamW(lr, weight_decay=1e-4), betas (0.9, 0.999), eps 1e-8) as ONE

@@ -52,7 +52,12 @@ class TensorChunk(ctypes.Structure):
                 ("shadow", ctypes.c_void_p), ("n", ctypes.c_int64)]
 
 
-_P, _I64, _I32, _F, _U32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint32
+class MixItem(ctypes.Structure):      # vit_mix_item, 24 bytes
+    _fields_ = [("src", ctypes.c_int32), ("w", ctypes.c_float), ("y0", ctypes.c_int32), ("y1", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("x1", ctypes.c_int32)]
+
+
+_P, _I64, _I32, _F, _U32 =ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint32
 
 # name: (restype, argtypes)
 _SIGS = {
@@ -97,6 +102,9 @@ _SIGS = {
     "vit_adamw_clipped": (ctypes.c_int, [_P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I32, _P, _P]),
     "vit_adamw_ema": (ctypes.c_int, [_P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I32, _F, _P, _P]),
     "vit_ema_swap": (ctypes.c_int, [_P, _P, _I64, _I32, _P]),
+    # added under ABI 18 (purely added entry points do not change the version, vit_hip.h)
+    "vit_softmax_xent_mixed": (ctypes.c_int, [_P, _P, _P, _P, _F, _I64, _I64, _P, _P, _P, _P]),
+    "vit_mix_batch": (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _I64, _I64, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -3,6 +3,7 @@
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -323,6 +324,93 @@ def softmax_xent(logits, labels, stream=None):
     _lib.call("vit_softmax_xent", _ptr(logits), _ptr(labels), rows, classes, _ptr(loss), _ptr(dlogits), _ptr(ws),
               _stream(stream))
     return loss, dlogits
+
+
+def softmax_xent_mixed(logits, labels_a, labels_b=None, lam=None, smoothing=0.0, stream=None):
+    """vit_softmax_xent_mixed: softmax_xent against the target (1 - smoothing) * (lam * onehot(a) + (1 - lam) *
+    onehot(b)) + smoothing / classes, which is never built.  `labels_b` int64 [rows] and `lam` float32 [rows] (the
+    weight of `labels_a`) on the logits' device, or both None.  Returns (loss [1] f32, dlogits [rows, classes] f32)."""
+    _need_cuda(logits, labels_a, labels_b, lam)
+    rows, classes = logits.shape
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("logits must be contiguous float32")
+    for name, t, dt in (("labels_a", labels_a, torch.int64), ("labels_b", labels_b, torch.int64),
+                        ("lam", lam, torch.float32)):
+        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()
+                              or t.device != logits.device):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {rows} elements on the logits' device")
+    if lam is not None and labels_b is None:
+        raise ValueError("lam given without labels_b")
+    if not 0.0 <= smoothing < 1.0:
+        raise ValueError(f"label smoothing must lie in [0, 1) (got {smoothing!r})")
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    ws = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    _lib.call("vit_softmax_xent_mixed", _ptr(logits), _ptr(labels_a), _ptr(labels_b), _ptr(lam), float(smoothing),
+              rows, classes, _ptr(loss), _ptr(dlogits), _ptr(ws), _stream(stream))
+    return loss, dlogits
+
+
+MIX_ITEM_BYTES = ctypes.sizeof(_lib.MixItem)      # vit_mix_item: int32 src, float w, int32 y0, y1, x0, x1
+_MIX_DTYPE = np.dtype([("src", "<i4"), ("w", "<f4"), ("y0", "<i4"), ("y1", "<i4"), ("x0", "<i4"), ("x1", "<i4")])
+assert _MIX_DTYPE.itemsize == MIX_ITEM_BYTES == 24
+
+
+def check_mix_table(src, w, y0, y1, x0, x1, B, H, W):
+    """The caller's contract of vit_mix_batch, which the kernel cannot check: six host sequences of B entries with
+    0 <= src < B, 0 <= w <= 1, 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W."""
+    cols = [np.asarray(c, dtype=np.float64 if k == 1 else np.int64) for k, c in enumerate((src, w, y0, y1, x0, x1))]
+    if any(c.shape != (B,) for c in cols):
+        raise ValueError(f"mix table: every column needs {B} entries")
+    s, wi, a0, a1, b0, b1 = cols
+    ok_src = (0 <= s) & (s < B)
+    ok_w = (0.0 <= wi) & (wi <= 1.0)                  # also refuses NaN
+    ok_box = (0 <= a0) & (a0 <= a1) & (a1 <= H) & (0 <= b0) & (b0 <= b1) & (b1 <= W)
+    bad = np.flatnonzero(~(ok_src & ok_w & ok_box))
+    if bad.size:
+        i = int(bad[0])
+        if not ok_src[i]:
+            raise ValueError(f"mix table row {i}: src {s[i]} outside [0, {B})")
+        if not ok_w[i]:
+            raise ValueError(f"mix table row {i}: w {wi[i]} outside [0, 1]")
+        raise ValueError(f"mix table row {i}: box rows [{a0[i]}, {a1[i]}) x columns [{b0[i]}, {b1[i]}) outside a "
+                         f"{H} x {W} image")
+    return cols
+
+
+def mix_table_host(src, w, y0, y1, x0, x1, pin=False):
+    """The vit_mix_item array of the six columns as a uint8 host tensor (pinned with `pin`)."""
+    B = len(src)
+    tab = np.zeros(B, dtype=_MIX_DTYPE)
+    for name, col in zip(("src", "w", "y0", "y1", "x0", "x1"), (src, w, y0, y1, x0, x1)):
+        tab[name] = col
+    host = torch.empty(B * MIX_ITEM_BYTES, dtype=torch.uint8, pin_memory=pin)
+    host.copy_(torch.from_numpy(tab.view(np.uint8)))
+    return host
+
+
+def mix_batch(x, table, out=None, stream=None):
+    """vit_mix_batch over a contiguous [B, C, H, W] float32 / bfloat16 device batch: out = x[src] inside each image's
+    box, w * x + (1 - w) * x[src] outside it (x itself, bitwise, where w == 1).  `table` = (src, w, y0, y1, x0, x1),
+    host sequences of B entries; it is validated here, BEFORE any device work (so a bad table raises without a GPU),
+    then uploaded from a fresh pinned tensor with a non-blocking copy: no host sync.  `x` is not modified."""
+    if x.dim() != 4:
+        raise ValueError("mix_batch: x must be [B, C, H, W]")
+    B, C, H, W = x.shape
+    cols = check_mix_table(*table, B, H, W)
+    _need_cuda(x, out)
+    if not x.is_contiguous():
+        raise ValueError("mix_batch: x must be contiguous")
+    if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device
+                            or not out.is_contiguous()):
+        raise ValueError("mix_batch: out must be a contiguous tensor of x's shape, dtype and device")
+    s = stream if stream is not None else torch.cuda.current_stream(x.device)
+    with torch.cuda.stream(s):                    # what is made here belongs to the stream that uses it
+        if out is None:
+            out = torch.empty_like(x)
+        items = mix_table_host(*cols, pin=True).to(x.device, non_blocking=True)
+    _lib.call("vit_mix_batch", _ptr(x), _ptr(out), dtype_code(x), B, C, H, W, _ptr(items), _stream(s))
+    return out
 
 
 def adamw(table_dev, nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale,

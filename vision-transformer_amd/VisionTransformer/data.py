@@ -14,10 +14,13 @@ Pillow), on a side stream one batch ahead of the training step.
   * `SyntheticRawImages` — deterministic uint8 images (optionally ragged sizes) for tests and benchmarks;
   * `collate_raw` / `raw_loader` — the packing collate and its DataLoader;
   * `GpuImageTransform(size)` — packed batch -> [B, 3, S, S] device tensor;
-  * `DeviceBatches(loader, transform, device)` — iterates (images on device, labels on device), prefetching the next
-    batch's copy + transform on a side stream;
+  * `DeviceBatches(loader, transform, device, mix=None)` — iterates (images on device, labels on device), prefetching
+    the next batch's copy + transform (+ mix) on a side stream;
+  * `BatchMix(mixup_alpha, cutmix_alpha, ...)` — mixup / CutMix of a batch in one kernel launch (`vit_mix_batch`),
+    labels as `optim.MixedLabels` (not in the reference);
   * `host_transform(size)` — the same transform on the host with Pillow (the CPU path, train.py --device cpu).
 """
+import collections
 import ctypes
 import glob
 import os
@@ -183,12 +186,114 @@ class GpuImageTransform:
         return out
 
 
+MixTable = collections.namedtuple("MixTable", "src w y0 y1 x0 x1 lam")
+
+
+class BatchMix:
+    """mixup and CutMix of a batch and its labels (not in the reference, whose only transform is the resize,
+    train.py:151-155; the recipe is timm's Mixup): `mix(x, y) -> (x_mixed, optim.MixedLabels)`.
+
+    Image i is paired with image B - 1 - i (timm's flip; the loader already shuffles).  With probability 1 - `prob`
+    nothing is mixed; otherwise CutMix is chosen with probability `switch_prob` when both alphas are > 0, else
+    whichever alpha is > 0.  mixup: lambda ~ Beta(alpha, alpha), x = lambda * x[i] + (1 - lambda) * x[B-1-i].  CutMix
+    (timm's rand_bbox with the corrected lambda): r = sqrt(1 - lambda), a box of int(H r) x int(W r) around a centre
+    uniform in the image, clipped to it, is taken from the partner, and lambda = 1 - box area / (H W).
+    `per_image=False` makes one draw for the whole batch, `True` one per image.
+
+    The RNG is numpy.random.default_rng([seed, rank]); `rank` defaults to the process group's rank (0 without one), so
+    replicas mix differently and no stream coincides with the weight-init seed.
+
+    Device tensors (float32 / bfloat16): one vit_mix_batch launch, out of place; the table and lambda are uploaded
+    from fresh pinned tensors by non-blocking copies; the partner labels are y.flip(0); no host sync.  Host tensors:
+    the same formula in torch ops.  `x` is never modified."""
+
+    def __init__(self, mixup_alpha=0.0, cutmix_alpha=0.0, prob=1.0, switch_prob=0.5, per_image=False, seed=0,
+                 rank=None):
+        if mixup_alpha < 0 or cutmix_alpha < 0 or not (mixup_alpha > 0 or cutmix_alpha > 0):
+            raise ValueError("BatchMix needs mixup_alpha > 0 or cutmix_alpha > 0 (and neither negative)")
+        if not (0.0 <= prob <= 1.0 and 0.0 <= switch_prob <= 1.0):
+            raise ValueError("BatchMix: prob and switch_prob must lie in [0, 1]")
+        if rank is None:
+            import torch.distributed as dist
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob, self.per_image = float(prob), float(switch_prob), bool(per_image)
+        self.seed, self.rank = int(seed), int(rank)
+        self._rng = np.random.default_rng([self.seed, self.rank])
+
+    def _draw_one(self, H, W):
+        """(w, y0, y1, x0, x1, lam) of one draw."""
+        rng = self._rng
+        if rng.random() >= self.prob:
+            return 1.0, 0, 0, 0, 0, 1.0
+        if self.mixup_alpha > 0 and self.cutmix_alpha > 0:
+            cut = rng.random() < self.switch_prob
+        else:
+            cut = self.cutmix_alpha > 0
+        if not cut:
+            lam = float(np.float32(rng.beta(self.mixup_alpha, self.mixup_alpha)))
+            return lam, 0, 0, 0, 0, lam
+        lam = rng.beta(self.cutmix_alpha, self.cutmix_alpha)
+        r = np.sqrt(1.0 - lam)
+        ch, cw = int(H * r), int(W * r)
+        cy, cx = int(rng.integers(H)), int(rng.integers(W))
+        y0, y1 = int(np.clip(cy - ch // 2, 0, H)), int(np.clip(cy + ch // 2, 0, H))
+        x0, x1 = int(np.clip(cx - cw // 2, 0, W)), int(np.clip(cx + cw // 2, 0, W))
+        return 1.0, y0, y1, x0, x1, 1.0 - (y1 - y0) * (x1 - x0) / (H * W)
+
+    def draw(self, B, H, W):
+        """The host table of the next batch: MixTable(src, w, y0, y1, x0, x1, lam), numpy arrays of B entries (int32
+        but w and lam, float32).  lam is the weight of image i's own label."""
+        rows = [self._draw_one(H, W) for _ in range(B if self.per_image else 1)]
+        if not self.per_image:
+            rows = rows * B
+        w, y0, y1, x0, x1, lam = zip(*rows)
+        i32 = lambda v: np.asarray(v, dtype=np.int32)     # noqa: E731
+        return MixTable(np.arange(B - 1, -1, -1, dtype=np.int32), np.asarray(w, dtype=np.float32), i32(y0), i32(y1),
+                        i32(x0), i32(x1), np.asarray(lam, dtype=np.float32))
+
+    @staticmethod
+    def mix_host(x, tab):
+        """The formula of vit_mix_batch in torch ops, on any device: inside the box x[src]; outside it x itself where
+        w == 1, else w * x + (1 - w) * x[src] in fp32 rounded once."""
+        B, _, H, W = x.shape
+        dev = x.device
+        col = lambda v, dt: torch.as_tensor(np.asarray(v), dtype=dt, device=dev).view(B, 1, 1, 1)     # noqa: E731
+        xs = x[torch.as_tensor(np.asarray(tab.src), dtype=torch.long, device=dev)]
+        ys = torch.arange(H, device=dev).view(1, 1, H, 1)
+        cs = torch.arange(W, device=dev).view(1, 1, 1, W)
+        y0, y1, x0, x1 = (col(v, torch.long) for v in (tab.y0, tab.y1, tab.x0, tab.x1))
+        box = (ys >= y0) & (ys < y1) & (cs >= x0) & (cs < x1)
+        w = col(tab.w, torch.float32)
+        blend = (w * x.float() + (1.0 - w) * xs.float()).to(x.dtype)
+        return torch.where(box, xs, torch.where(w == 1.0, x, blend))
+
+    def __call__(self, x, y, stream=None):
+        from . import _ops
+        from .optim import MixedLabels
+        if x.dim() != 4 or y.shape[0] != x.shape[0]:
+            raise ValueError("BatchMix: x must be [B, C, H, W] and y must have B entries")
+        B, _, H, W = x.shape
+        tab = self.draw(B, H, W)
+        if not x.is_cuda:
+            return self.mix_host(x, tab), MixedLabels(y.long(), y.long().flip(0), torch.from_numpy(tab.lam.copy()))
+        s = stream if stream is not None else torch.cuda.current_stream(x.device)
+        out = _ops.mix_batch(x.contiguous(), tab[:6], stream=s)
+        with torch.cuda.stream(s):
+            a = y.to(x.device, non_blocking=True).long()
+            lam = torch.from_numpy(tab.lam).pin_memory().to(x.device, non_blocking=True)
+            labels = MixedLabels(a, a.flip(0), lam)       # src_i = B - 1 - i: the gather is a flip
+        return out, labels
+
+
 class DeviceBatches:
     """Iterate a raw loader as (images [B, 3, S, S] on device, labels on device): the next batch's host->device copy
-    and GPU transform are issued on a side stream while the caller's step runs on the current one."""
+    and GPU transform are issued on a side stream while the caller's step runs on the current one.  With `mix` (a
+    BatchMix) the mix is staged on the side stream directly after the resize, one batch ahead like it, and the
+    iterator yields (mixed images, optim.MixedLabels)."""
 
-    def __init__(self, loader, transform, device):
-        self.loader, self.transform, self.device = loader, transform, torch.device(device)
+    def __init__(self, loader, transform, device, mix=None):
+        self.loader, self.transform, self.device, self.mix = loader, transform, torch.device(device), mix
 
     def __len__(self):
         return len(self.loader)
@@ -198,6 +303,8 @@ class DeviceBatches:
         with torch.cuda.stream(stream):
             x = self.transform(packed, meta, self.device, stream=stream)
             y = labels.to(self.device, non_blocking=True)
+            if self.mix is not None:
+                x, y = self.mix(x, y, stream=stream)
             ev = torch.cuda.Event()
             ev.record(stream)
         return x, y, ev
@@ -213,8 +320,8 @@ class DeviceBatches:
         while nxt is not None:
             x, y, ev = nxt
             torch.cuda.current_stream(self.device).wait_event(ev)
-            x.record_stream(torch.cuda.current_stream(self.device))
-            y.record_stream(torch.cuda.current_stream(self.device))
+            for t in (x, *(y if isinstance(y, tuple) else (y,))):      # every tensor the side stream made
+                t.record_stream(torch.cuda.current_stream(self.device))
             try:
                 nxt = self._stage(next(it), side)
             except StopIteration:

@@ -6,11 +6,13 @@ engine reads (bf16 copies of the fp32 masters), so no separate cast pass runs pe
 ('step', 'exp_avg', 'exp_avg_sq') are those of torch.optim.AdamW, so `optimizer.state_dict()` checkpoints are
 interchangeable with the reference's (train.py:73,110).
 
-CrossEntropyLoss: nn.CrossEntropyLoss() (mean) as one fused softmax + NLL + gradient kernel.
+CrossEntropyLoss: nn.CrossEntropyLoss() (mean) as one fused softmax + NLL + gradient kernel; with `label_smoothing`
+and / or MixedLabels (mixup / CutMix) the same against a smoothed two-label target that is never materialised.
 """
 import collections
 import contextlib
 import math
+import typing
 
 import torch
 import torch.nn as nn
@@ -397,12 +399,70 @@ class _XentFn(torch.autograd.Function):
         return dlogits * g, None
 
 
-def cross_entropy(logits, labels):
+class MixedLabels(typing.NamedTuple):
+    """The labels of a mixed batch (data.BatchMix): row i's target is lam[i] * onehot(a[i]) + (1 - lam[i]) *
+    onehot(b[i]).  `a`, `b` int64 [rows], `lam` float32 [rows], all on the logits' device."""
+    a: torch.Tensor
+    b: torch.Tensor
+    lam: torch.Tensor
+
+
+def dense_target(labels, classes, label_smoothing=0.0, dtype=torch.float32):
+    """The [rows, classes] target that cross_entropy's kernel never builds: (1 - eps) * (lam * onehot(a) + (1 - lam) *
+    onehot(b)) + eps / classes for MixedLabels, the smoothed one-hot for a label tensor.  The host path and the tests
+    use it."""
+    if isinstance(labels, MixedLabels):
+        a, b, lam = labels.a.long(), labels.b.long(), labels.lam.to(dtype)
+    else:
+        a = b = labels.long()
+        lam = torch.ones(a.shape[0], dtype=dtype, device=a.device)
+    t = torch.zeros(a.shape[0], classes, dtype=dtype, device=a.device)
+    t.scatter_add_(1, a[:, None], lam[:, None])
+    t.scatter_add_(1, b[:, None], (1 - lam)[:, None])
+    return t * (1.0 - label_smoothing) + label_smoothing / classes
+
+
+class _XentMixedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, a, b, lam, smoothing):
+        loss, dlogits = _ops.softmax_xent_mixed(logits.contiguous().float(), a, b, lam, smoothing)
+        ctx.save_for_backward(dlogits)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g, None, None, None, None
+
+
+def _check_label_smoothing(label_smoothing):
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1) (got {label_smoothing!r})")
+
+
+def cross_entropy(logits, labels, label_smoothing=0.0):
     """mean softmax cross-entropy (nn.CrossEntropyLoss() default) — fused HIP kernel, gradient precomputed; host
-    tensors (the CPU path) use torch's own."""
+    tensors (the CPU path) use torch's own.
+
+    `label_smoothing` (torch's keyword) and `labels` given as MixedLabels (mixup / CutMix, data.BatchMix) are not in
+    the reference (train.py:81).  A label tensor with label_smoothing == 0 runs vit_softmax_xent exactly as before;
+    anything else runs vit_softmax_xent_mixed, which forms the smoothed two-label target on the fly.  On the host:
+    F.cross_entropy(..., label_smoothing=), on the dense two-hot target for MixedLabels."""
+    _check_label_smoothing(label_smoothing)
+    mixed = isinstance(labels, MixedLabels)
     if not logits.is_cuda:
-        return nn.functional.cross_entropy(logits, labels)
-    return _XentFn.apply(logits, labels)
+        if mixed:
+            return nn.functional.cross_entropy(logits, dense_target(labels, logits.shape[-1], dtype=logits.dtype),
+                                               label_smoothing=label_smoothing)
+        if label_smoothing == 0.0:
+            return nn.functional.cross_entropy(logits, labels)
+        return nn.functional.cross_entropy(logits, labels, label_smoothing=label_smoothing)
+    if not mixed:
+        if label_smoothing == 0.0:
+            return _XentFn.apply(logits, labels)
+        return _XentMixedFn.apply(logits, labels.contiguous().long(), None, None, float(label_smoothing))
+    return _XentMixedFn.apply(logits, labels.a.contiguous().long(), labels.b.contiguous().long(),
+                              labels.lam.contiguous().float(), float(label_smoothing))
 
 
 def _check_max_grad_norm(max_grad_norm):
@@ -521,7 +581,13 @@ def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda", max_grad_n
 
 
 class CrossEntropyLoss(nn.Module):
-    """Drop-in for nn.CrossEntropyLoss() as used by the reference (train.py:81): mean reduction, no weights."""
+    """Drop-in for nn.CrossEntropyLoss() as used by the reference (train.py:81): mean reduction, no weights.
+    `label_smoothing` mirrors torch's keyword; `labels` may be MixedLabels (cross_entropy)."""
+
+    def __init__(self, label_smoothing=0.0):
+        super().__init__()
+        _check_label_smoothing(label_smoothing)
+        self.label_smoothing = label_smoothing
 
     def forward(self, logits, labels):
-        return cross_entropy(logits, labels)
+        return cross_entropy(logits, labels, self.label_smoothing)

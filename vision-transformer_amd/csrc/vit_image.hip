@@ -120,6 +120,143 @@ __global__ __launch_bounds__(256) void resize_apply_kernel(const uint8_t* __rest
   st1<TO>(o + 2 * plane, (float)clip8(acc2) / 255.0f);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Batch mix (vit_hip.h "Batch mix"): out[i] = x[src_i] inside image i's box, w_i * x[i] + (1 - w_i) * x[src_i] outside
+// it — mixup (empty box), CutMix (w = 1) and the unmixed image (w = 1, empty box) in one streaming kernel.
+// One lane owns U units of one image, a unit being 16 bytes of one row (VEC = 4 fp32 / 8 bf16 elements) or, where the
+// pointers or the row length do not allow that, one element (VEC = 1).  The image's table entry is workgroup-uniform.
+// All loads of a lane's units are issued before the math; a unit outside the box of a w = 1 image never reads x[src],
+// a unit inside the box never reads x[i], and a 16-byte unit that a box edge cuts is done element by element, each
+// element read from the one image it needs.
+// ---------------------------------------------------------------------------------------------------------------
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <class T, int VEC> struct MixUnit { typedef u32x4 type; };
+template <class T> struct MixUnit<T, 1> { typedef T type; };
+
+// the one blend both forms use, so that they agree bit for bit: w1 = 1 - w formed once per image
+VIT_DEV float mix1(float a, float b, float w, float w1) { return fmaf(w, a, w1 * b); }
+
+VIT_DEV float mix_unit(float a, float b, float w, float w1) { return mix1(a, b, w, w1); }
+VIT_DEV bf16_t mix_unit(bf16_t a, bf16_t b, float w, float w1) { return f2bf(mix1(bf2f(a), bf2f(b), w, w1)); }
+template <class T> VIT_DEV u32x4 mix_unit16(u32x4 a, u32x4 b, float w, float w1);
+template <> VIT_DEV u32x4 mix_unit16<float>(u32x4 a, u32x4 b, float w, float w1) {
+  u32x4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = __float_as_uint(mix1(__uint_as_float(a[k]), __uint_as_float(b[k]), w, w1));
+  return r;
+}
+template <> VIT_DEV u32x4 mix_unit16<bf16_t>(u32x4 a, u32x4 b, float w, float w1) {
+  u32x4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float lo = mix1(__uint_as_float(a[k] << 16), __uint_as_float(b[k] << 16), w, w1);
+    const float hi = mix1(__uint_as_float(a[k] & 0xffff0000u), __uint_as_float(b[k] & 0xffff0000u), w, w1);
+    r[k] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+  }
+  return r;
+}
+template <class T, int VEC> VIT_DEV typename MixUnit<T, VEC>::type mix_blend(typename MixUnit<T, VEC>::type a,
+                                                                             typename MixUnit<T, VEC>::type b,
+                                                                             float w, float w1) {
+  if constexpr (VEC == 1) return mix_unit(a, b, w, w1);
+  else return mix_unit16<T>(a, b, w, w1);
+}
+
+// one element as the 32 bits it waits in
+VIT_DEV uint32_t mix_raw(float v) { return __float_as_uint(v); }
+VIT_DEV uint32_t mix_raw(bf16_t v) { return v; }
+template <class T> VIT_DEV T mix_unraw(uint32_t r);
+template <> VIT_DEV float mix_unraw<float>(uint32_t r) { return __uint_as_float(r); }
+template <> VIT_DEV bf16_t mix_unraw<bf16_t>(uint32_t r) { return (bf16_t)r; }
+
+enum { MIX_SKIP = 0, MIX_OUTSIDE = 1, MIX_INSIDE = 2, MIX_CUT = 3 };
+
+// nu: units per image, upr: units per row (W / VEC), bpi: workgroups per image, n: elements per image
+template <class T, int VEC, int U>
+__global__ __launch_bounds__(256) void mix_batch_kernel(const T* __restrict__ x, T* __restrict__ out,
+                                                        const vit_mix_item* __restrict__ items, uint32_t nu,
+                                                        uint32_t upr, uint32_t H, uint32_t bpi, int64_t n) {
+  typedef typename MixUnit<T, VEC>::type R;
+  const uint32_t img = blockIdx.x / bpi;
+  const uint32_t chunk = blockIdx.x - img * bpi;
+  const vit_mix_item it = items[img];
+  const bool keep = it.w == 1.0f;                 // outside the box the image is its own, bitwise
+  const float w = it.w, w1 = 1.0f - it.w;
+  const T* xi = x + (int64_t)img * n;
+  const T* xs = x + (int64_t)it.src * n;
+  T* o = out + (int64_t)img * n;
+  uint32_t e[U];                                  // first element of the unit within the image
+  int xv[U], mode[U];
+  R a[U], b[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint32_t v = chunk * (256u * U) + (uint32_t)u * 256u + threadIdx.x;
+    mode[u] = MIX_SKIP;
+    e[u] = 0;
+    xv[u] = 0;
+    if (v < nu) {
+      const uint32_t row = v / upr;
+      const int y = (int)(row % H);
+      xv[u] = (int)(v - row * upr) * VEC;
+      e[u] = v * VEC;
+      const bool rowin = y >= it.y0 && y < it.y1;
+      if (!rowin || xv[u] + VEC <= it.x0 || xv[u] >= it.x1) mode[u] = MIX_OUTSIDE;
+      else if (xv[u] >= it.x0 && xv[u] + VEC <= it.x1) mode[u] = MIX_INSIDE;
+      else mode[u] = MIX_CUT;
+    }
+    if (mode[u] == MIX_OUTSIDE) a[u] = *reinterpret_cast<const R*>(xi + e[u]);
+    if (mode[u] == MIX_INSIDE || (mode[u] == MIX_OUTSIDE && !keep)) b[u] = *reinterpret_cast<const R*>(xs + e[u]);
+    if constexpr (VEC > 1) {
+      // A unit with a box edge inside it (its row is inside the box's rows; a random box gives most box rows two):
+      // element by element, every element from the one image it needs — x[src] inside the box, x[i] outside —, issued
+      // here with the other loads.  Element j waits, unconverted, in the unit's a / b registers (j < 4 / j >= 4).
+      if (mode[u] == MIX_CUT) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          const int xx = xv[u] + j;
+          const uint32_t raw = mix_raw(((xx >= it.x0 && xx < it.x1) ? xs : xi)[e[u] + j]);
+          if (j < 4) a[u][j] = raw;
+          else b[u][j - 4] = raw;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (mode[u] == MIX_OUTSIDE) {
+      *reinterpret_cast<R*>(o + e[u]) = keep ? a[u] : mix_blend<T, VEC>(a[u], b[u], w, w1);
+    } else if (mode[u] == MIX_INSIDE) {
+      *reinterpret_cast<R*>(o + e[u]) = b[u];
+    }
+    if constexpr (VEC > 1) {
+      if (mode[u] == MIX_CUT) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          const int xx = xv[u] + j;
+          T r = mix_unraw<T>(j < 4 ? a[u][j] : b[u][j - 4]);
+          // only a blended image with a box (w < 1 and a box, which BatchMix never draws) needs a second element
+          if (!keep && !(xx >= it.x0 && xx < it.x1)) r = mix_unit(r, xs[e[u] + j], w, w1);
+          o[e[u] + j] = r;
+        }
+      }
+    }
+  }
+}
+
+template <class T>
+static void mix_batch_launch(const void* x, void* out, int64_t B, int64_t n, int64_t H, int64_t W, bool vec,
+                             int64_t bpi, const vit_mix_item* items, hipStream_t s) {
+  constexpr int VEC = 16 / (int)sizeof(T), U = 4;
+  const unsigned grid = (unsigned)(bpi * B);
+  if (vec)
+    mix_batch_kernel<T, VEC, U><<<grid, 256, 0, s>>>((const T*)x, (T*)out, items, (uint32_t)(n / VEC),
+                                                     (uint32_t)(W / VEC), (uint32_t)H, (uint32_t)bpi, n);
+  else
+    mix_batch_kernel<T, 1, U><<<grid, 256, 0, s>>>((const T*)x, (T*)out, items, (uint32_t)n, (uint32_t)W,
+                                                   (uint32_t)H, (uint32_t)bpi, n);
+}
+
 }  // namespace
 
 extern "C" int vit_resize_ksize(int64_t in_size, int64_t out_size) {
@@ -153,4 +290,28 @@ extern "C" int vit_resize_to_tensor(const void* src, const int64_t* meta, int64_
   else
     resize_apply_kernel<bf16_t><<<g2, 256, 0, s>>>((const uint8_t*)src, meta, oh, ow, ks, tab, (bf16_t*)out);
   return vit::check_launch("vit_resize_to_tensor");
+}
+
+extern "C" int vit_mix_batch(const void* x, void* out, int32_t dtype, int64_t B, int64_t C, int64_t H, int64_t W,
+                             const vit_mix_item* items_dev, void* stream) {
+  VIT_REQUIRE(x && out && items_dev, "vit_mix_batch: null pointer");
+  VIT_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "vit_mix_batch: non-positive dimension (B %lld, C %lld, H %lld, W %lld)",
+              (long long)B, (long long)C, (long long)H, (long long)W);
+  VIT_REQUIRE(dtype == VIT_F32 || dtype == VIT_BF16, "vit_mix_batch: bad dtype %d", (int)dtype);
+  const int64_t lim = 0x7fffffff, esize = dtype == VIT_F32 ? 4 : 2;
+  // one image is indexed in 32 bits, the batch in 64
+  VIT_REQUIRE(C <= lim && H <= lim && W <= lim && C * H <= lim / W, "vit_mix_batch: an image of 2^31 elements or more");
+  const int64_t n = C * H * W;
+  const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out;
+  const bool vec = ((xa | oa) & 15) == 0 && (W * esize) % 16 == 0;
+  const int64_t nu = vec ? n / (16 / esize) : n;
+  const int64_t bpi = (nu + 1023) / 1024;         // 256 lanes x 4 units per workgroup
+  VIT_REQUIRE(B <= lim / bpi, "vit_mix_batch: batch too large (%lld workgroups)", (long long)B * (long long)bpi);
+  const uint64_t bytes = (uint64_t)B * (uint64_t)n * (uint64_t)esize;
+  // the mix reads image src after writing image i: in place (or any overlap) cannot be right
+  VIT_REQUIRE(xa + bytes <= oa || oa + bytes <= xa, "vit_mix_batch: out overlaps x");
+  hipStream_t s = VIT_STREAM(stream);
+  if (dtype == VIT_F32) mix_batch_launch<float>(x, out, B, n, H, W, vec, bpi, items_dev, s);
+  else mix_batch_launch<bf16_t>(x, out, B, n, H, W, vec, bpi, items_dev, s);
+  return vit::check_launch("vit_mix_batch");
 }

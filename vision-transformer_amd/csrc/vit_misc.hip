@@ -337,6 +337,65 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float* __restrict_
   if (tid == 0) row_loss[r] = lse - x[y];
 }
 
+// xent_rows_kernel against the two-label smoothed target t = (1 - eps) * (lam * onehot(a) + (1 - lam) * onehot(b)) +
+// eps / C, which is never stored (vit_hip.h "vit_softmax_xent_mixed").  Everything is relative to the row maximum, the
+// sum over the classes included: t sums to 1, so the maximum cancels and x - 16 gives the same loss to rounding.
+// labels_b == NULL: b = a; lam == NULL: lam = 1.  A label outside [0, classes) gives a NaN loss, not a stray read.
+__global__ __launch_bounds__(256) void xent_mixed_rows_kernel(const float* __restrict__ logits,
+                                                              const int64_t* __restrict__ labels_a,
+                                                              const int64_t* __restrict__ labels_b,
+                                                              const float* __restrict__ lam, float smoothing,
+                                                              int64_t classes, float inv_rows,
+                                                              float* __restrict__ dlogits,
+                                                              float* __restrict__ row_loss) {
+  __shared__ float red[4];
+  __shared__ float red2[4];
+  const int64_t r = blockIdx.x;
+  const float* x = logits + r * classes;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  float mx = -INFINITY;
+  for (int64_t c = tid; c < classes; c += 256) mx = fmaxf(mx, x[c]);
+  mx = wave_max(mx);
+  if (lane == 0) red[w] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float s = 0.f, z = 0.f;                               // sum exp(x - mx), sum (x - mx)
+  for (int64_t c = tid; c < classes; c += 256) {
+    const float d = x[c] - mx;
+    s += __expf(d);
+    z += d;
+  }
+  s = wave_sum(s);
+  z = wave_sum(z);
+  if (lane == 0) {
+    red[w] = s;
+    red2[w] = z;
+  }
+  __syncthreads();
+  s = red[0] + red[1] + red[2] + red[3];
+  z = red2[0] + red2[1] + red2[2] + red2[3];
+  const float lse = mx + __logf(s);
+  const int64_t ya = labels_a[r];
+  const int64_t yb = labels_b ? labels_b[r] : ya;
+  const float l = (lam && labels_b) ? lam[r] : 1.f;
+  const float keep = 1.f - smoothing;
+  const float ta = keep * l, tb = keep * (1.f - l), tu = smoothing / (float)classes;
+  for (int64_t c = tid; c < classes; c += 256) {
+    const float p = __expf(x[c] - lse);
+    const float t = (c == ya ? ta : 0.f) + (c == yb ? tb : 0.f) + tu;
+    dlogits[r * classes + c] = (p - t) * inv_rows;
+  }
+  if (tid == 0) {
+    const float za = (ya >= 0 && ya < classes) ? x[ya] - mx : NAN;
+    const float zb = (yb >= 0 && yb < classes) ? x[yb] - mx : NAN;
+    // a label of weight 0 contributes nothing, whatever its logit holds (lam in {0, 1}, or no partner at all)
+    float v = __logf(s) - ((ta != 0.f ? ta * za : 0.f) + (tb != 0.f ? tb * zb : 0.f));
+    if (smoothing != 0.f) v -= tu * z;                  // eps = 0: a -inf logit must not turn 0 * -inf into NaN
+    row_loss[r] = v;
+  }
+}
+
 __global__ __launch_bounds__(256) void xent_reduce_kernel(const float* __restrict__ row_loss, int64_t rows,
                                                           float inv_rows, float* __restrict__ loss) {
   __shared__ float red[4];
@@ -733,6 +792,24 @@ extern "C" int vit_softmax_xent(const float* logits, const int64_t* labels, int6
   xent_rows_kernel<<<(unsigned)rows, 256, 0, s>>>(logits, labels, classes, inv, dlogits, workspace);
   xent_reduce_kernel<<<1, 256, 0, s>>>(workspace, rows, inv, loss);
   return vit::check_launch("vit_softmax_xent");
+}
+
+extern "C" int vit_softmax_xent_mixed(const float* logits, const int64_t* labels_a, const int64_t* labels_b,
+                                      const float* lam, float smoothing, int64_t rows, int64_t classes, float* loss,
+                                      float* dlogits, float* workspace, void* stream) {
+  VIT_REQUIRE(logits && labels_a && loss && dlogits && workspace, "vit_softmax_xent_mixed: null pointer");
+  VIT_REQUIRE(rows > 0 && classes > 0, "vit_softmax_xent_mixed: rows and classes must be positive (got %lld, %lld)",
+              (long long)rows, (long long)classes);
+  VIT_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "vit_softmax_xent_mixed: smoothing must lie in [0, 1) (got %g)",
+              (double)smoothing);
+  VIT_REQUIRE(!lam || labels_b, "vit_softmax_xent_mixed: lam given without labels_b");
+  VIT_REQUIRE(rows <= 0x7fffffff, "vit_softmax_xent_mixed: too many rows for one grid (%lld)", (long long)rows);
+  hipStream_t s = VIT_STREAM(stream);
+  const float inv = 1.0f / (float)rows;
+  xent_mixed_rows_kernel<<<(unsigned)rows, 256, 0, s>>>(logits, labels_a, labels_b, lam, smoothing, classes, inv,
+                                                        dlogits, workspace);
+  xent_reduce_kernel<<<1, 256, 0, s>>>(workspace, rows, inv, loss);
+  return vit::check_launch("vit_softmax_xent_mixed");
 }
 
 // Host side of the chunk-table launchers.  What the three AdamW entry points check alike, reported under the name

@@ -31,7 +31,7 @@ import torch
 import torch.distributed as dist
 
 from VisionTransformer import config, vit
-from VisionTransformer.optim import cross_entropy, make_optimizer
+from VisionTransformer.optim import MixedLabels, cross_entropy, make_optimizer
 
 device = "cuda" if torch.cuda.is_available() else "cpu"
 
@@ -193,7 +193,8 @@ def _rank_world():
 
 
 def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkpoint_dir, lr=1e-4,
-          log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None, ema_decay=None):
+          log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None, ema_decay=None,
+          label_smoothing=0.0, mix=None):
     """The reference training loop (train.py:60-119) on the HIP path.  Returns the last epoch's summed loss.
 
     Defaults keep the GPU busy: no host sync inside the epoch — the epoch loss is summed on the device and the per-step
@@ -213,7 +214,15 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     `ema_decay` (not in the reference either): the optimizer keeps an exponential moving average of the weights inside
     its step (optim.make_optimizer), validation scores the EMA weights (swapped in for `evaluate` and out again), and
     the checkpoint dict gains one key, "ema_state_dict" — the model's state_dict with the EMA in place of every trained
-    parameter.  Resuming needs nothing more: the EMA is part of "optimizer_state_dict"."""
+    parameter.  Resuming needs nothing more: the EMA is part of "optimizer_state_dict".
+
+    `label_smoothing` and `mix` (not in the reference, whose loss is the plain cross entropy of the hard labels,
+    train.py:81): the training loss is cross_entropy(..., label_smoothing=), and `mix` (a data.BatchMix) mixes every
+    batch after it reached the device — mixup / CutMix, labels as MixedLabels — unless the loader already yielded
+    MixedLabels (data.DeviceBatches(mix=...) stages the mix one batch ahead).  The logged "Loss/train_batch", the epoch
+    loss and the checkpoint's "loss" are then the smoothed / mixed loss, not the hard-label cross entropy.  evaluate()
+    and validation see unmixed data and hard labels.  Under data parallelism nothing more is needed: the mix is
+    per-rank input work before the forward, and BatchMix seeds itself per rank."""
     rank, world = _rank_world()
     saved_epoch = search_checkpoint(checkpoint_dir)
     torch.manual_seed(0)                              # identical init on every rank
@@ -256,9 +265,12 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
         nb = 0
         for tensors, labels in train_loader:
             tensors = tensors.to(device, non_blocking=True)
-            labels = labels.to(device, non_blocking=True)
+            if not isinstance(labels, MixedLabels):   # else the loader mixed already (data.DeviceBatches(mix=))
+                labels = labels.to(device, non_blocking=True)
+                if mix is not None:
+                    tensors, labels = mix(tensors, labels)
             logits = net(tensors)
-            loss = cross_entropy(logits, labels)
+            loss = cross_entropy(logits, labels, label_smoothing)
             optimizer.zero_grad(set_to_none=True)
             loss.backward()
             optimizer.step()
@@ -311,11 +323,13 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     return running_loss
 
 
-def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None, ema_decay=None):
+def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None, ema_decay=None,
+               label_smoothing=0.0, mix=None):
     """The hot loop body (train.py:91-98: forward, CE loss, zero_grad(set_to_none), backward, AdamW step) on one
     synthetic batch already resident on `dev`, dropout on; returns (seconds per timed step, last loss).  This is the
     repo's own CPU training step that bench.py's `cpu_baseline` times (BASELINE config 1).  Unclipped unless
-    `max_grad_norm` is given, and without a weight EMA unless `ema_decay` is."""
+    `max_grad_norm` is given, and without a weight EMA unless `ema_decay` is.  With `mix` (a data.BatchMix) every step
+    first mixes the resident batch, and `label_smoothing` goes to the loss, as in train()."""
     dev = torch.device(dev or device)
     torch.manual_seed(0)
     model = vit.VisionTransformer(configs).to(dev).train()
@@ -332,7 +346,8 @@ def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_no
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
-        loss = cross_entropy(model(x), y)
+        xb, yb = (x, y) if mix is None else mix(x, y)
+        loss = cross_entropy(model(xb), yb, label_smoothing)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
@@ -360,6 +375,16 @@ def main():
     ap.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
                     help="keep an exponential moving average of the weights with this decay inside the optimizer "
                          "step, validate on it and save it as ema_state_dict (default: none, as the reference)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="F",
+                    help="label smoothing of the training loss (default 0: the reference's plain cross entropy)")
+    ap.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
+                    help="mixup with lambda ~ Beta(ALPHA, ALPHA) on the training batches (default 0: off)")
+    ap.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
+                    help="CutMix with lambda ~ Beta(ALPHA, ALPHA) on the training batches (default 0: off)")
+    ap.add_argument("--mix-prob", type=float, default=1.0, metavar="P",
+                    help="probability that a batch is mixed at all (with --mixup / --cutmix)")
+    ap.add_argument("--mix-switch-prob", type=float, default=0.5, metavar="P",
+                    help="probability of CutMix when both --mixup and --cutmix are on")
     ap.add_argument("--reference-loop", action="store_true",
                     help="the reference's loop bookkeeping exactly: validate every epoch, restart the step counter on "
                          "resume, host-summed loss (train.py:60-119)")
@@ -397,10 +422,14 @@ def main():
     cfg = config.ViTConfig(input_channels=3, num_classes=args.classes, num_patches=n_patches, embedding_size=D,
                            patch_size=args.patch, num_heads=H, num_blocks=L, precision=dtype,
                            batch_size=args.batch, device="cpu")
+    mix = None
+    if args.mixup > 0 or args.cutmix > 0:
+        from VisionTransformer.data import BatchMix
+        mix = BatchMix(args.mixup, args.cutmix, prob=args.mix_prob, switch_prob=args.mix_switch_prob)
     if args.bench:
         steps = args.steps or 30
         sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm,
-                               ema_decay=args.ema_decay)
+                               ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix)
         print(json.dumps({"device": device, "model": args.model, "img": args.img, "batch": args.batch,
                           "dtype": args.dtype, "threads": torch.get_num_threads(), "warmup": args.warmup,
                           "steps": steps, "ms_per_step": round(sec * 1e3, 3),
@@ -427,7 +456,8 @@ def main():
         from VisionTransformer import data as D
         # one transform (and coefficient workspace) per loader: each stages its batches on its own side stream
         train_loader = D.DeviceBatches(D.raw_loader(train_set, args.batch, shuffle=True, num_workers=args.workers,
-                                                    sampler=sampler), D.GpuImageTransform(args.img), device)
+                                                    sampler=sampler), D.GpuImageTransform(args.img), device,
+                                      mix=mix)
         test_loader = D.DeviceBatches(D.raw_loader(test_set, args.batch, shuffle=False, num_workers=args.workers,
                                                    drop_last=False, sampler=tsampler), D.GpuImageTransform(args.img),
                                       device)
@@ -443,7 +473,7 @@ def main():
                                                   sampler=tsampler, drop_last=False, pin_memory=pin)
     train(cfg, train_loader, test_loader, args.epochs, args.eval_iter, args.log_dir, args.checkpoint_dir,
           lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop, max_grad_norm=args.clip_grad_norm,
-          ema_decay=args.ema_decay)
+          ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix)
     if world > 1:
         dist.destroy_process_group()
 
