@@ -66,6 +66,8 @@ const char* vit_last_error(void);
  *   "splitk_rounds"      1: rounds of 256 workgroups the weight-gradient K split aims at (vit_gemm_split_k_hint)
  *   "attn_fwd_grid"      0 (automatic: one workgroup per CU): workgroups of the persistent ring attention forward
  *                        when the call's own max_wgs is 0
+ *   "augment_path"       0 (automatic): 1 forces the direct form of vit_augment_to_tensor, 2 its tiled two-pass form
+ *                        wherever a tile's row span fits (see "Training augmentation" below)
  * ABI 15 removed the one-workgroup-per-head attention forward, which lost its A/B runs, together with the option name
  * that selected it: vit_set_option refuses that name.
  * ABI 16 removed the 128x128-tile second launch for a last partial round of 256x256 tiles, which measured slower (33.0
@@ -75,7 +77,8 @@ const char* vit_last_error(void);
  * ABI 18 adds the weight-EMA entry points (vit_adamw_ema, vit_ema_swap), likewise with no option name.
  * Since ABI 18, entry points that are purely added do not change the version: a host that needs one checks for the
  * symbol (dlsym, or a link error).  The version changes only when an existing signature or meaning does.  Added under
- * 18 this way: vit_softmax_xent_mixed and vit_mix_batch (label smoothing, mixup and CutMix), with no option name.
+ * 18 this way: vit_softmax_xent_mixed and vit_mix_batch (label smoothing, mixup and CutMix), with no option name;
+ * vit_augment_workspace_bytes and vit_augment_to_tensor (crop, flip, normalize, erase), with "augment_path".
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -294,6 +297,50 @@ int vit_resize_ksize(int64_t in_size, int64_t out_size);
 int64_t vit_resize_workspace_bytes(int64_t B, int64_t out_h, int64_t out_w, int64_t ksize);
 int vit_resize_to_tensor(const void* src, const int64_t* meta, int64_t B, int64_t out_h, int64_t out_w, int64_t ksize,
                          void* out, int32_t out_dtype, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Training augmentation inside the resize launch (not in the reference, whose only transform is the resize,
+ * train.py:151-155): random resized crop, horizontal flip, normalize and a constant-fill erase of the same packed
+ * batch, as torchvision's RandomResizedCrop + RandomHorizontalFlip on the PIL image, ToTensor, Normalize(mean, std)
+ * and timm's RandomErasing(mode='const') give.  items_dev[i] (DEVICE memory) describes image i:
+ *   crop   img.convert('RGB').crop((x0, y0, x0+cw, y0+ch)).resize((out_w, out_h), BILINEAR), bit-exact with Pillow:
+ *          the coefficients are those of cw -> out_w and ch -> out_h and the taps are clamped to the crop, not to the
+ *          image (Image.resize(box=) clamps to the image and is a different picture);
+ *   flip   out[..., x] = resized[..., out_w-1-x];
+ *   value  with mean3 / std3 (HOST float[3] each): ((float)v / 255.0f - mean[c]) / std[c], two IEEE fp32 operations
+ *          after the division by 255, bitwise torch's (x - mean) / std on the ToTensor output; without: v / 255.0f;
+ *   erase  inside rows [ey0, ey1) x columns [ex0, ex1) of the OUTPUT (after the flip) the value is erase_value and
+ *          none of that pixel's source taps is read.
+ * The bf16 output is the fp32 value rounded once (nearest even).  ksize is the max over the batch of
+ * vit_resize_ksize(cw, out_w) and vit_resize_ksize(ch, out_h).  An identity table (full-image box, no flip, empty
+ * erase box, no mean) gives vit_resize_to_tensor bit for bit.
+ * The entry point cannot read the table, so the coefficient kernel clamps every box to its image (x0 into [0, w-1],
+ * cw into [1, w-x0], rows likewise) and an erase box acts only where it meets the output: a bad table gives a wrong
+ * picture, never a read outside the image's bytes [off, off + h*w*c).
+ * Two forms compute the same bits.  The direct form is vit_resize_to_tensor's schedule (every output pixel runs the
+ * horizontal pass once per vertical tap).  The tiled form gives one workgroup VIT_AUG_TILE_ROWS x VIT_AUG_TILE_COLS
+ * output pixels: it runs the horizontal pass once per source row that the tile's vertical taps reach, into LDS, and
+ * the vertical pass out of LDS (Pillow's own two-pass schedule); a tile whose taps reach more than
+ * VIT_AUG_TILE_MAX_SPAN source rows takes the direct form, decided per workgroup.  Option "augment_path": 0 chooses
+ * per launch (the tiled form up to ksize 9, the range where every tile fits and where it measured faster, DESIGN.md
+ * §5; the direct form above), 1 the direct form everywhere, 2 the tiled form wherever the span fits.
+ * Refused: NULL src / meta / items_dev / out / workspace, only one of mean3 / std3, a zero or non-finite std, a
+ * non-finite mean or erase_value, a dtype other than VIT_F32 / VIT_BF16, the size limits of vit_resize_to_tensor, a
+ * workspace smaller than vit_augment_workspace_bytes.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define VIT_AUG_TILE_ROWS 16
+#define VIT_AUG_TILE_COLS 64
+#define VIT_AUG_TILE_MAX_SPAN 80
+typedef struct vit_aug_item {
+  int32_t x0, y0, cw, ch;     /* crop box in source pixels: columns [x0, x0+cw), rows [y0, y0+ch) */
+  int32_t flip;               /* 1: mirror the output left-right */
+  int32_t ey0, ey1, ex0, ex1; /* erase box in output pixels (after the flip); empty when ey1<=ey0 or ex1<=ex0 */
+} vit_aug_item; /* 36 bytes */
+int64_t vit_augment_workspace_bytes(int64_t B, int64_t out_h, int64_t out_w, int64_t ksize);
+int vit_augment_to_tensor(const void* src, const int64_t* meta, const vit_aug_item* items_dev, int64_t B,
+                          int64_t out_h, int64_t out_w, int64_t ksize, const float* mean3, const float* std3,
+                          float erase_value, void* out, int32_t out_dtype, void* workspace, int64_t workspace_bytes,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Batch mix: mixup and CutMix of a contiguous [B][C][H][W] batch, out of place, in one streaming launch (the

@@ -57,6 +57,13 @@ class MixItem(ctypes.Structure):      # vit_mix_item, 24 bytes
                 ("x0", ctypes.c_int32), ("x1", ctypes.c_int32)]
 
 
+class AugItem(ctypes.Structure):      # vit_aug_item, 36 bytes
+    _fields_ = [(n, ctypes.c_int32) for n in ("x0", "y0", "cw", "ch", "flip", "ey0", "ey1", "ex0", "ex1")]
+
+
+# the tiled form of vit_augment_to_tensor (vit_hip.h VIT_AUG_TILE_*): tile rows x columns, most source rows of a tile
+AUG_TILE_ROWS, AUG_TILE_COLS, AUG_TILE_MAX_SPAN = 16, 64, 80
+
 _P, _I64, _I32, _F, _U32 =ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint32
 
 # name: (restype, argtypes)
@@ -105,6 +112,8 @@ _SIGS = {
     # added under ABI 18 (purely added entry points do not change the version, vit_hip.h)
     "vit_softmax_xent_mixed": (ctypes.c_int, [_P, _P, _P, _P, _F, _I64, _I64, _P, _P, _P, _P]),
     "vit_mix_batch": (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _I64, _I64, _P, _P]),
+    "vit_augment_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
+    "vit_augment_to_tensor": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _F, _P, _I32, _P, _I64, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

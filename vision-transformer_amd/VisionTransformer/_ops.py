@@ -413,6 +413,95 @@ def mix_batch(x, table, out=None, stream=None):
     return out
 
 
+AUG_ITEM_BYTES = ctypes.sizeof(_lib.AugItem)      # vit_aug_item: nine int32
+AUG_COLUMNS = ("x0", "y0", "cw", "ch", "flip", "ey0", "ey1", "ex0", "ex1")
+_AUG_DTYPE = np.dtype([(n, "<i4") for n in AUG_COLUMNS])
+assert _AUG_DTYPE.itemsize == AUG_ITEM_BYTES == 36
+
+
+def check_aug_table(table, heights, widths, out_h, out_w):
+    """The table of vit_augment_to_tensor, which the entry point cannot read: nine host sequences (AUG_COLUMNS) of B
+    entries with the crop box inside its image (0 <= x0, 1 <= cw, x0 + cw <= W; rows likewise), flip 0 or 1 and the
+    erase box inside the output (0 <= ey0 <= ey1 <= out_h, 0 <= ex0 <= ex1 <= out_w).  Returns the int64 columns."""
+    H, W = np.asarray(heights, dtype=np.int64), np.asarray(widths, dtype=np.int64)
+    B = H.shape[0]
+    if len(table) != len(AUG_COLUMNS):
+        raise ValueError(f"augment table: {len(AUG_COLUMNS)} columns expected ({', '.join(AUG_COLUMNS)})")
+    cols = [np.asarray(c, dtype=np.int64) for c in table]
+    if any(c.shape != (B,) for c in cols) or W.shape != (B,):
+        raise ValueError(f"augment table: every column needs {B} entries")
+    x0, y0, cw, ch, flip, ey0, ey1, ex0, ex1 = cols
+    ok_box = (0 <= x0) & (1 <= cw) & (x0 + cw <= W) & (0 <= y0) & (1 <= ch) & (y0 + ch <= H)
+    ok_flip = (flip == 0) | (flip == 1)
+    ok_erase = (0 <= ey0) & (ey0 <= ey1) & (ey1 <= out_h) & (0 <= ex0) & (ex0 <= ex1) & (ex1 <= out_w)
+    bad = np.flatnonzero(~(ok_box & ok_flip & ok_erase))
+    if bad.size:
+        i = int(bad[0])
+        if not ok_box[i]:
+            raise ValueError(f"augment table row {i}: crop columns [{x0[i]}, {x0[i] + cw[i]}) x rows [{y0[i]}, "
+                             f"{y0[i] + ch[i]}) is empty or outside its {H[i]} x {W[i]} image")
+        if not ok_flip[i]:
+            raise ValueError(f"augment table row {i}: flip {flip[i]} is neither 0 nor 1")
+        raise ValueError(f"augment table row {i}: erase rows [{ey0[i]}, {ey1[i]}) x columns [{ex0[i]}, {ex1[i]}) "
+                         f"outside a {out_h} x {out_w} output")
+    return cols
+
+
+def aug_table_host(table, pin=False):
+    """The vit_aug_item array of the nine columns as a uint8 host tensor (pinned with `pin`)."""
+    B = len(table[0])
+    tab = np.zeros(B, dtype=_AUG_DTYPE)
+    for name, col in zip(AUG_COLUMNS, table):
+        tab[name] = col
+    host = torch.empty(B * AUG_ITEM_BYTES, dtype=torch.uint8, pin_memory=pin)
+    host.copy_(torch.from_numpy(tab.view(np.uint8)))
+    return host
+
+
+def aug_ksize(cw, ch, out_h, out_w):
+    """ksize of vit_augment_to_tensor for crops of the given widths and heights: the most taps of any axis."""
+    lib = _lib.load()
+    return max(max(lib.vit_resize_ksize(int(a), out_w) for a in np.unique(cw)),
+               max(lib.vit_resize_ksize(int(a), out_h) for a in np.unique(ch)))
+
+
+def check_mean_std(mean, std):
+    """(mean, std) as two float triples, or (None, None): both or neither, mean finite, std finite and non-zero."""
+    if mean is None and std is None:
+        return None, None
+    if mean is None or std is None:
+        raise ValueError("normalize: mean and std go together")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("normalize: mean and std need 3 entries each")
+    if not all(np.isfinite(mean)) or not all(np.isfinite(std)) or any(s == 0.0 for s in std):
+        raise ValueError("normalize: mean must be finite, std finite and non-zero")
+    return mean, std
+
+
+def augment_to_tensor(src, meta, items, out_h, out_w, ksize, out, workspace=None, mean=None, std=None,
+                      erase_value=0.0, stream=None):
+    """vit_augment_to_tensor: `src` the packed uint8 batch, `meta` int64 [B, 4] and `items` the vit_aug_item array
+    (uint8, aug_table_host's layout), all on the device; `out` [B, 3, out_h, out_w] float32 / bfloat16.  The table is
+    NOT validated here (it is device memory; the kernel clamps it): data.GpuTrainTransform validates on the host
+    before it uploads.  One launch on `stream`, no host sync."""
+    mean, std = check_mean_std(mean, std)
+    _need_cuda(src, meta, items, out, workspace)
+    B = meta.shape[0]
+    if items.numel() * items.element_size() != B * AUG_ITEM_BYTES:
+        raise ValueError(f"augment_to_tensor: the table needs {B} items of {AUG_ITEM_BYTES} bytes")
+    if tuple(out.shape) != (B, 3, out_h, out_w) or not out.is_contiguous():
+        raise ValueError(f"augment_to_tensor: out must be a contiguous [{B}, 3, {out_h}, {out_w}] tensor")
+    need = _lib.load().vit_augment_workspace_bytes(B, out_h, out_w, ksize)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=out.device)
+    f3 = ctypes.c_float * 3
+    _lib.call("vit_augment_to_tensor", _ptr(src), _ptr(meta), _ptr(items), B, out_h, out_w, ksize,
+              f3(*mean) if mean else None, f3(*std) if std else None, float(erase_value), _ptr(out),
+              dtype_code(out), _ptr(workspace), workspace.numel(), _stream(stream))
+    return out
+
+
 def adamw(table_dev, nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale,
           shadow_dtype, stream=None, clip=None):
     """vit_adamw; with `clip` (the [4] f32 device block grad_clip_finish wrote) vit_adamw_clipped: the gradient

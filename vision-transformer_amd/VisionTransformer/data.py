@@ -18,7 +18,10 @@ Pillow), on a side stream one batch ahead of the training step.
     the next batch's copy + transform (+ mix) on a side stream;
   * `BatchMix(mixup_alpha, cutmix_alpha, ...)` — mixup / CutMix of a batch in one kernel launch (`vit_mix_batch`),
     labels as `optim.MixedLabels` (not in the reference);
-  * `host_transform(size)` — the same transform on the host with Pillow (the CPU path, train.py --device cpu).
+  * `host_transform(size)` — the same transform on the host with Pillow (the CPU path, train.py --device cpu);
+  * `TrainAugment(...)` / `GpuTrainTransform(size, augment, ...)` — random resized crop, horizontal flip, normalize
+    and constant erase inside the resize launch (`vit_augment_to_tensor`; not in the reference), and
+    `host_train_transform(size, augment, ...)`, the same on the host.
 """
 import collections
 import ctypes
@@ -145,25 +148,75 @@ def raw_loader(dataset, batch_size, shuffle=True, num_workers=4, drop_last=True,
                                        persistent_workers=num_workers > 0)
 
 
-class GpuImageTransform:
-    """convert('RGB') -> Resize((S, S)) (PIL bilinear) -> ToTensor on the GPU: packed batch -> [B, 3, S, S]."""
+def _checked_meta(packed, meta):
+    """The batch's meta on the host, after the checks that keep the kernels inside `packed`."""
+    meta_h = meta.cpu() if meta.is_cuda else meta
+    if meta_h.shape[0] == 0:
+        raise ValueError("empty batch")
+    off, h, w, c = (meta_h[:, i] for i in range(4))
+    if (h <= 0).any() or (w <= 0).any() or not ((c >= 1) & (c <= 4)).all():
+        raise ValueError("invalid image metadata")
+    if int((off + h * w * c).max()) > packed.numel() or (off < 0).any():
+        raise ValueError("image metadata points outside the packed buffer")
+    return meta_h
 
-    def __init__(self, size, dtype=torch.float32):
+
+AugTable = collections.namedtuple("AugTable", "x0 y0 cw ch flip ey0 ey1 ex0 ex1")
+
+
+def identity_table(meta):
+    """The AugTable that augments nothing: the full image, no flip, no erase box."""
+    m = np.asarray(meta, dtype=np.int64).reshape(-1, 4)
+    z = np.zeros(m.shape[0], dtype=np.int32)
+    return AugTable(z, z, m[:, 2].astype(np.int32), m[:, 1].astype(np.int32), z, z, z, z, z)
+
+
+def _augment_launch(tf, packed, meta_h, table, device, stream, erase_value=0.0):
+    """One vit_augment_to_tensor launch of transform `tf` (its size, dtype, mean, std and workspace) over a packed
+    batch with the host AugTable `table`, validated here BEFORE anything is uploaded.  The table goes up from a fresh
+    pinned tensor by a non-blocking copy on the launch's stream: no host sync."""
+    from . import _ops
+    sh, sw = tf.size
+    m = meta_h.numpy()
+    cols = _ops.check_aug_table(table, m[:, 1], m[:, 2], sh, sw)
+    ks = _ops.aug_ksize(cols[2], cols[3], sh, sw)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    B = meta_h.shape[0]
+    with torch.cuda.stream(s):
+        src = packed.to(dev, non_blocking=True)
+        meta_d = meta_h.to(dev, non_blocking=True)
+        items = _ops.aug_table_host(cols, pin=True).to(dev, non_blocking=True)
+        need = _lib.load().vit_augment_workspace_bytes(B, sh, sw, ks)
+        if tf._ws is None or tf._ws.numel() < need or tf._ws.device != dev:
+            tf._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=dev)
+        out = torch.empty(B, 3, sh, sw, dtype=tf.dtype, device=dev)
+    _ops.augment_to_tensor(src, meta_d, items, sh, sw, ks, out, tf._ws, mean=tf.mean, std=tf.std,
+                           erase_value=erase_value, stream=s)
+    if stream is not None:
+        for t in (src, meta_d, items, tf._ws):
+            t.record_stream(stream)
+    return out
+
+
+class GpuImageTransform:
+    """convert('RGB') -> Resize((S, S)) (PIL bilinear) -> ToTensor on the GPU: packed batch -> [B, 3, S, S].  With the
+    keyword-only `mean` / `std` (evaluation beside a normalised training run) also Normalize(mean, std)."""
+
+    def __init__(self, size, dtype=torch.float32, *, mean=None, std=None):
+        from . import _ops
         self.size = (size, size) if isinstance(size, int) else tuple(size)
         self.dtype = dtype
+        self.mean, self.std = _ops.check_mean_std(mean, std)
         self._ws = None
 
     def __call__(self, packed, meta, device=None, stream=None):
-        meta_h = meta.cpu() if meta.is_cuda else meta
+        meta_h = _checked_meta(packed, meta)
         B = meta_h.shape[0]
         sh, sw = self.size
-        if B == 0:
-            raise ValueError("empty batch")
         off, h, w, c = (meta_h[:, i] for i in range(4))
-        if (h <= 0).any() or (w <= 0).any() or not ((c >= 1) & (c <= 4)).all():
-            raise ValueError("invalid image metadata")
-        if int((off + h * w * c).max()) > packed.numel() or (off < 0).any():
-            raise ValueError("image metadata points outside the packed buffer")
+        if self.mean is not None:      # evaluation with Normalize: the augmenting launch with an identity table
+            return _augment_launch(self, packed, meta_h, identity_table(meta_h), device, stream)
         lib = _lib.load()
         ks = max(max(lib.vit_resize_ksize(int(a), sh) for a in h.unique()),
                  max(lib.vit_resize_ksize(int(a), sw) for a in w.unique()))
@@ -184,6 +237,118 @@ class GpuImageTransform:
             for t in (src, meta_d, self._ws):
                 t.record_stream(stream)
         return out
+
+
+class TrainAugment:
+    """The geometric training augmentation's draws (not in the reference, whose only transform is the resize,
+    train.py:151-155): torchvision's RandomResizedCrop.get_params and RandomHorizontalFlip, timm's RandomErasing
+    (mode='const') box.  `draw(meta, out_h, out_w)` returns the host AugTable of one batch, one entry per image.
+
+    Crop: up to 10 attempts of area * U(scale), aspect exp(U(log r0, log r1)), w = int(round(sqrt(a r))),
+    h = int(round(sqrt(a / r))), accepted if 0 < w <= W and 0 < h <= H and placed uniformly; else the central box with
+    the aspect clamped into `ratio` and the long side whole.  `scale=None`: the full image.  Flip: with probability
+    `hflip`.  Erase: with probability `erase_prob`, up to 10 attempts of (out area) * U(erase_scale), log-uniform
+    aspect, h = int(round(sqrt(a r))), w = int(round(sqrt(a / r))), accepted if h < out_h and w < out_w and placed
+    uniformly; else no box.  The box is in output pixels, after the flip, and is filled with `erase_value` after the
+    normalize (timm erases the normalised tensor, before mixup).
+
+    The RNG is numpy.random.default_rng([seed, rank]) as in BatchMix; `rank` defaults to the process group's."""
+
+    def __init__(self, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, erase_prob=0.0, erase_scale=(0.02, 1 / 3),
+                 erase_ratio=(0.3, 3.3), erase_value=0.0, seed=0, rank=None):
+        def pair(v, name, top=None):
+            lo, hi = (float(a) for a in v)
+            if not (0.0 < lo <= hi) or (top is not None and hi > top):
+                raise ValueError(f"TrainAugment: {name} must be 0 < lo <= hi" + (f" <= {top}" if top else ""))
+            return lo, hi
+        self.scale = None if scale is None else pair(scale, "scale", 1.0)
+        self.ratio = pair(ratio, "ratio")
+        self.erase_scale, self.erase_ratio = pair(erase_scale, "erase_scale", 1.0), pair(erase_ratio, "erase_ratio")
+        if not (0.0 <= hflip <= 1.0 and 0.0 <= erase_prob <= 1.0):
+            raise ValueError("TrainAugment: hflip and erase_prob must lie in [0, 1]")
+        if not np.isfinite(erase_value):
+            raise ValueError("TrainAugment: erase_value must be finite")
+        if rank is None:
+            import torch.distributed as dist
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.hflip, self.erase_prob, self.erase_value = float(hflip), float(erase_prob), float(erase_value)
+        self.seed, self.rank = int(seed), int(rank)
+        self.reseed()
+
+    def reseed(self, *more):
+        """Restart the stream from [seed, rank, *more] (host_train_transform: one stream per DataLoader worker)."""
+        self._rng = np.random.default_rng([self.seed, self.rank, *(int(v) for v in more)])
+
+    def crop_box(self, H, W):
+        """(x0, y0, cw, ch, fallback) of one RandomResizedCrop draw on an H x W image."""
+        if self.scale is None:
+            return 0, 0, W, H, False
+        rng = self._rng
+        area = H * W
+        l0, l1 = np.log(self.ratio[0]), np.log(self.ratio[1])
+        for _ in range(10):
+            a = area * rng.uniform(self.scale[0], self.scale[1])
+            r = float(np.exp(rng.uniform(l0, l1)))
+            w, h = int(round(float(np.sqrt(a * r)))), int(round(float(np.sqrt(a / r))))
+            if 0 < w <= W and 0 < h <= H:
+                y0 = int(rng.integers(0, H - h + 1))
+                x0 = int(rng.integers(0, W - w + 1))
+                return x0, y0, w, h, False
+        in_ratio = W / H
+        if in_ratio < self.ratio[0]:
+            w, h = W, int(round(W / self.ratio[0]))
+        elif in_ratio > self.ratio[1]:
+            w, h = int(round(H * self.ratio[1])), H
+        else:
+            w, h = W, H
+        w, h = min(max(w, 1), W), min(max(h, 1), H)
+        return (W - w) // 2, (H - h) // 2, w, h, True
+
+    def erase_box(self, out_h, out_w):
+        """(ey0, ey1, ex0, ex1) of one RandomErasing draw; an empty box (zeros) when nothing is erased."""
+        rng = self._rng
+        if self.erase_prob <= 0.0 or rng.random() >= self.erase_prob:
+            return 0, 0, 0, 0
+        area = out_h * out_w
+        l0, l1 = np.log(self.erase_ratio[0]), np.log(self.erase_ratio[1])
+        for _ in range(10):
+            a = area * rng.uniform(self.erase_scale[0], self.erase_scale[1])
+            r = float(np.exp(rng.uniform(l0, l1)))
+            h, w = int(round(float(np.sqrt(a * r)))), int(round(float(np.sqrt(a / r))))
+            if h < out_h and w < out_w:
+                y0 = int(rng.integers(0, out_h - h + 1))
+                x0 = int(rng.integers(0, out_w - w + 1))
+                return y0, y0 + h, x0, x0 + w
+        return 0, 0, 0, 0
+
+    def draw(self, meta, out_h, out_w):
+        """The host AugTable of the next batch from its meta [B, 4] = (offset, H, W, C): int32 numpy arrays.  Per
+        image the draws are taken in the order crop, flip, erase."""
+        rows = []
+        for _, H, W, _ in np.asarray(meta, dtype=np.int64).reshape(-1, 4).tolist():
+            x0, y0, cw, ch, _ = self.crop_box(H, W)
+            flip = int(self.hflip > 0.0 and self._rng.random() < self.hflip)
+            rows.append((x0, y0, cw, ch, flip, *self.erase_box(out_h, out_w)))
+        return AugTable(*(np.asarray(c, dtype=np.int32) for c in zip(*rows)))
+
+
+class GpuTrainTransform:
+    """The training transform on the GPU: RandomResizedCrop -> RandomHorizontalFlip -> ToTensor -> Normalize ->
+    RandomErasing of a packed batch in ONE vit_augment_to_tensor launch (bit-exact with Pillow's crop().resize()),
+    called like GpuImageTransform, so DeviceBatches takes it unchanged.  The table is drawn on the host from `meta`
+    (`augment`, a TrainAugment), validated, and uploaded by a non-blocking copy on the launch's stream."""
+
+    def __init__(self, size, augment, dtype=torch.float32, mean=None, std=None):
+        from . import _ops
+        self.size = (size, size) if isinstance(size, int) else tuple(size)
+        self.augment, self.dtype = augment, dtype
+        self.mean, self.std = _ops.check_mean_std(mean, std)
+        self._ws = None
+
+    def __call__(self, packed, meta, device=None, stream=None):
+        meta_h = _checked_meta(packed, meta)
+        table = self.augment.draw(meta_h.numpy(), *self.size)
+        return _augment_launch(self, packed, meta_h, table, device, stream, erase_value=self.augment.erase_value)
 
 
 MixTable = collections.namedtuple("MixTable", "src w y0 y1 x0 x1 lam")
@@ -343,9 +508,19 @@ class Transformed(torch.utils.data.Dataset):
         return self.tf(x), y
 
 
-def host_transform(size):
-    """The reference transform on the host (Pillow): convert('RGB') -> resize((S, S), BILINEAR) -> /255 CHW."""
+def _mean_std_columns(mean, std):
+    from . import _ops
+    mean, std = _ops.check_mean_std(mean, std)
+    if mean is None:
+        return None, None
+    return (torch.tensor(v, dtype=torch.float32).view(3, 1, 1) for v in (mean, std))
+
+
+def host_transform(size, *, mean=None, std=None):
+    """The reference transform on the host (Pillow): convert('RGB') -> resize((S, S), BILINEAR) -> /255 CHW; with the
+    keyword-only `mean` / `std` then (x - mean) / std per channel."""
     sh, sw = (size, size) if isinstance(size, int) else size
+    mean_c, std_c = _mean_std_columns(mean, std)
 
     def tf(img):
         from PIL import Image
@@ -354,5 +529,42 @@ def host_transform(size):
         if img.mode != "RGB":
             img = img.convert("RGB")
         a = np.asarray(img.resize((sw, sh), Image.BILINEAR), dtype=np.uint8)
-        return torch.from_numpy(a.astype(np.float32) / np.float32(255.0)).permute(2, 0, 1).contiguous()
+        x = torch.from_numpy(a.astype(np.float32) / np.float32(255.0)).permute(2, 0, 1).contiguous()
+        return x if mean_c is None else (x - mean_c) / std_c
+    return tf
+
+
+def host_train_transform(size, augment, mean=None, std=None):
+    """GpuTrainTransform on the host, per item, with Pillow and torch ops (train.py --device cpu): crop().resize(),
+    transpose(FLIP_LEFT_RIGHT), /255, (x - mean) / std, erase fill — the table drawn per image by `augment` (a
+    TrainAugment).  In a DataLoader worker the augment's stream is restarted once from [seed, rank, worker id, the
+    worker's seed], so the workers' copies of `augment` do not repeat each other."""
+    sh, sw = (size, size) if isinstance(size, int) else size
+    mean_c, std_c = _mean_std_columns(mean, std)
+    seeded = set()
+
+    def tf(img):
+        from PIL import Image
+        info = torch.utils.data.get_worker_info()
+        if info is not None and info.id not in seeded:
+            seeded.add(info.id)
+            augment.reseed(info.id, info.seed)
+        if not isinstance(img, Image.Image):
+            img = Image.fromarray(np.asarray(img, dtype=np.uint8))
+        if img.mode != "RGB":
+            img = img.convert("RGB")
+        W, H = img.size
+        t = augment.draw(np.array([[0, H, W, 3]], dtype=np.int64), sh, sw)
+        x0, y0, cw, ch, flip, ey0, ey1, ex0, ex1 = (int(c[0]) for c in t)
+        if not (0 <= x0 and 1 <= cw and x0 + cw <= W and 0 <= y0 and 1 <= ch and y0 + ch <= H):
+            raise ValueError(f"augment table: crop ({x0}, {y0}, {cw}, {ch}) is empty or outside its {H} x {W} image")
+        img = img.crop((x0, y0, x0 + cw, y0 + ch)).resize((sw, sh), Image.BILINEAR)
+        if flip:
+            img = img.transpose(Image.FLIP_LEFT_RIGHT)
+        a = np.asarray(img, dtype=np.uint8)
+        x = torch.from_numpy(a.astype(np.float32) / np.float32(255.0)).permute(2, 0, 1).contiguous()
+        if mean_c is not None:
+            x = (x - mean_c) / std_c
+        x[:, max(ey0, 0):ey1, max(ex0, 0):ex1] = augment.erase_value
+        return x
     return tf

@@ -143,7 +143,8 @@ void colsum_parts_launch(const void* x, int64_t ldx, int dtype, int64_t rows, in
   X(OPT_ATTN_FWD_GRID, "attn_fwd_grid", 0)          \
   X(OPT_ATTN_BWD_GRID, "attn_bwd_grid", 0)          \
   X(OPT_LN16, "ln16", 1)                            \
-  X(OPT_LN_AL, "ln_al", 1)
+  X(OPT_LN_AL, "ln_al", 1)                          \
+  X(OPT_AUGMENT_PATH, "augment_path", 0)
 namespace vit {
 enum Opt : int {
 #define X(ENUM, NAME, DEF) ENUM,

@@ -121,6 +121,220 @@ __global__ __launch_bounds__(256) void resize_apply_kernel(const uint8_t* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Training augmentation in the resize launch (vit_hip.h "Training augmentation"): the crop is another source window
+// per image (the coefficient tables are those of the crop's size, their bounds offset by the crop's origin), the flip
+// a mirrored store column, the normalize another final scale, the erase a pixel that reads no tap.  The tables have
+// vit_resize_to_tensor's layout.  Two apply kernels give the same bits: the direct one is resize_apply_kernel's
+// schedule; the tiled one runs the horizontal pass once per source row of a tile's row span into LDS (one dword per
+// pixel: the three clip8'd channels) and the vertical pass out of it.
+// ---------------------------------------------------------------------------------------------------------------
+// Automatic dispatch: the tiled form up to this ksize (scale <= 4, where every tile's row span fits: 16 x 4 + 2 x 4
+// rows), the range it was measured in and won (ksize 3 and 7); the direct form above it.
+constexpr int AUG_TILED_MAX_KS = 9;
+
+struct AugNorm {        // kernel argument; on == 0: the value is v / 255
+  float mean[3], sd[3];
+  int on;
+};
+
+// one axis of a crop box, clamped to its image: the origin into [0, size-1], the extent into [1, size-origin]
+VIT_DEV void clamp_box(int& o, int& n, int size) {
+  o = o < 0 ? 0 : (o > size - 1 ? size - 1 : o);
+  n = n < 1 ? 1 : (n > size - o ? size - o : n);
+}
+
+__global__ __launch_bounds__(256) void augment_coeffs_kernel(const int64_t* __restrict__ meta,
+                                                             const vit_aug_item* __restrict__ items, int oh, int ow,
+                                                             int ks, int* __restrict__ tab) {
+  const int b = blockIdx.y;
+  const ImgMeta m = reinterpret_cast<const ImgMeta*>(meta)[b];
+  const vit_aug_item it = items[b];
+  int x0 = it.x0, cw = it.cw, y0 = it.y0, ch = it.ch;
+  clamp_box(x0, cw, (int)m.w);
+  clamp_box(y0, ch, (int)m.h);
+  const int64_t per = (int64_t)(ow + oh) * (2 + ks);
+  int* t = tab + b * per;
+  int* bw = t;
+  int* bh = bw + 2 * ow;
+  int* kw = bh + 2 * oh;
+  int* kh = kw + (int64_t)ow * ks;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ow + oh; i += gridDim.x * blockDim.x) {
+    if (i < ow) {
+      axis_coeffs(i, cw, ow, ks, bw + 2 * i, kw + (int64_t)i * ks);
+      bw[2 * i] += x0;                     // taps stay inside the crop: [x0 + lo, x0 + lo + n) with lo + n <= cw
+    } else {
+      axis_coeffs(i - ow, ch, oh, ks, bh + 2 * (i - ow), kh + (int64_t)(i - ow) * ks);
+      bh[2 * (i - ow)] += y0;
+    }
+  }
+}
+
+// ToTensor (+ Normalize): uint8 / 255, then (t - mean) / std, every operation IEEE and on its own
+VIT_DEV float aug_value(int v, float mean, float sd, bool on) {
+#pragma clang fp contract(off)
+  const float t = (float)v / 255.0f;
+  return on ? (t - mean) / sd : t;
+}
+
+// Pixel (x, y) of the resized crop in resize_apply_kernel's arithmetic; kwt / kht: the image's k_w / k_h tables.
+VIT_DEV void resize_pixel(const uint8_t* __restrict__ img, int W, int C, const int* __restrict__ bw,
+                          const int* __restrict__ bh, const int* __restrict__ kwt, const int* __restrict__ kht, int ks,
+                          int x, int y, int& r0, int& r1, int& r2) {
+  const int* kw = kwt + (int64_t)x * ks;
+  const int* kh = kht + (int64_t)y * ks;
+  const int xlo = bw[2 * x], xn = bw[2 * x + 1];
+  const int ylo = bh[2 * y], yn = bh[2 * y + 1];
+  const int c1 = C >= 3 ? 1 : 0, c2 = C >= 3 ? 2 : 0;
+  int acc0 = 1 << (PREC - 1), acc1 = acc0, acc2 = acc0;
+  for (int j = 0; j < yn; ++j) {
+    const uint8_t* row = img + (int64_t)(ylo + j) * W * C;
+    int h0 = 1 << (PREC - 1), h1 = h0, h2 = h0;
+    for (int i = 0; i < xn; ++i) {
+      const uint8_t* px = row + (int64_t)(xlo + i) * C;
+      const int kk = kw[i];
+      h0 += (int)px[0] * kk;
+      h1 += (int)px[c1] * kk;
+      h2 += (int)px[c2] * kk;
+    }
+    const int kv = kh[j];
+    acc0 += clip8(h0) * kv;
+    acc1 += clip8(h1) * kv;
+    acc2 += clip8(h2) * kv;
+  }
+  r0 = clip8(acc0);
+  r1 = clip8(acc1);
+  r2 = clip8(acc2);
+}
+
+VIT_DEV bool aug_erased(const vit_aug_item& it, int y, int xs) {
+  return y >= it.ey0 && y < it.ey1 && xs >= it.ex0 && xs < it.ex1;
+}
+
+template <class TO>
+__global__ __launch_bounds__(256) void augment_apply_kernel(const uint8_t* __restrict__ src,
+                                                            const int64_t* __restrict__ meta,
+                                                            const vit_aug_item* __restrict__ items, int oh, int ow,
+                                                            int ks, const int* __restrict__ tab, AugNorm nm, float ev,
+                                                            TO* __restrict__ out) {
+  const int b = blockIdx.z;
+  const int y = blockIdx.y;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;       // column of the resized crop
+  if (x >= ow) return;
+  const vit_aug_item it = items[b];
+  const int xs = it.flip ? ow - 1 - x : x;                   // column it is stored at
+  const int64_t plane = (int64_t)oh * ow;
+  TO* o = out + (int64_t)b * 3 * plane + (int64_t)y * ow + xs;
+  if (aug_erased(it, y, xs)) {
+    st1<TO>(o, ev);
+    st1<TO>(o + plane, ev);
+    st1<TO>(o + 2 * plane, ev);
+    return;
+  }
+  const ImgMeta m = reinterpret_cast<const ImgMeta*>(meta)[b];
+  const int* bw = tab + b * ((int64_t)(ow + oh) * (2 + ks));
+  const int* bh = bw + 2 * ow;
+  const int* kwt = bh + 2 * oh;
+  int v0, v1, v2;
+  resize_pixel(src + m.off, (int)m.w, (int)m.c, bw, bh, kwt, kwt + (int64_t)ow * ks, ks, x, y, v0, v1, v2);
+  st1<TO>(o, aug_value(v0, nm.mean[0], nm.sd[0], nm.on));
+  st1<TO>(o + plane, aug_value(v1, nm.mean[1], nm.sd[1], nm.on));
+  st1<TO>(o + 2 * plane, aug_value(v2, nm.mean[2], nm.sd[2], nm.on));
+}
+
+// One workgroup per tile of TR output rows x TC output columns of one image; lane (lx, ly) owns column lx of the tile
+// and its rows ly, ly + 4, ...  The item, the meta and the tile's row span [r0, r1) are workgroup-uniform.  Only
+// 256 x 3 distinct output values exist: they are formed once per workgroup, with aug_value's arithmetic, in LDS.
+template <class TO>
+__global__ __launch_bounds__(256) void augment_tiled_kernel(const uint8_t* __restrict__ src,
+                                                            const int64_t* __restrict__ meta,
+                                                            const vit_aug_item* __restrict__ items, int oh, int ow,
+                                                            int ks, const int* __restrict__ tab, AugNorm nm, float ev,
+                                                            TO* __restrict__ out) {
+  constexpr int TR = VIT_AUG_TILE_ROWS, TC = VIT_AUG_TILE_COLS, SPAN = VIT_AUG_TILE_MAX_SPAN;
+  static_assert(TC == 64 && TR % 4 == 0, "a wave owns one row of the tile, a workgroup four");
+  __shared__ uint32_t hp[SPAN * TC];       // horizontal pass: [source row - r0][column], channels in bytes 0..2
+  __shared__ float val[3 * 256];           // output value of byte v in channel c
+  const int b = blockIdx.z;
+  const int ty0 = blockIdx.y * TR;
+  const int tyn = oh - ty0 < TR ? oh - ty0 : TR;
+  const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+  const int x = blockIdx.x * TC + lx;
+  const vit_aug_item it = items[b];
+  const ImgMeta m = reinterpret_cast<const ImgMeta*>(meta)[b];
+  const int xs = it.flip ? ow - 1 - x : x;
+  const int* bw = tab + b * ((int64_t)(ow + oh) * (2 + ks));
+  const int* bh = bw + 2 * ow;
+  const int* kwt = bh + 2 * oh;
+  const int* kht = kwt + (int64_t)ow * ks;
+  const uint8_t* img = src + m.off;
+  const int C = (int)m.c, W = (int)m.w;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) val[c * 256 + threadIdx.x] = aug_value((int)threadIdx.x, nm.mean[c], nm.sd[c], nm.on);
+  int r0 = 0x7fffffff, r1 = 0;
+  for (int r = 0; r < tyn; ++r) {
+    const int lo = bh[2 * (ty0 + r)], n = bh[2 * (ty0 + r) + 1];
+    r0 = lo < r0 ? lo : r0;
+    r1 = lo + n > r1 ? lo + n : r1;
+  }
+  const bool fits = r1 - r0 <= SPAN;       // else this tile takes the direct form below
+  if (fits) {
+    // a column whose every pixel in this tile is erased reads nothing
+    const bool dead = xs >= it.ex0 && xs < it.ex1 && ty0 >= it.ey0 && ty0 + tyn <= it.ey1;
+    if (x < ow && !dead) {
+      const int xlo = bw[2 * x], xn = bw[2 * x + 1];
+      const int* kw = kwt + (int64_t)x * ks;
+      const int c1 = C >= 3 ? 1 : 0, c2 = C >= 3 ? 2 : 0;
+      for (int r = r0 + ly; r < r1; r += 4) {
+        const uint8_t* row = img + (int64_t)r * W * C;
+        int h0 = 1 << (PREC - 1), h1 = h0, h2 = h0;
+        for (int i = 0; i < xn; ++i) {
+          const uint8_t* px = row + (int64_t)(xlo + i) * C;
+          const int kk = kw[i];
+          h0 += (int)px[0] * kk;
+          h1 += (int)px[c1] * kk;
+          h2 += (int)px[c2] * kk;
+        }
+        hp[(r - r0) * TC + lx] = (uint32_t)clip8(h0) | ((uint32_t)clip8(h1) << 8) | ((uint32_t)clip8(h2) << 16);
+      }
+    }
+  }
+  __syncthreads();
+  if (x >= ow) return;
+  const int64_t plane = (int64_t)oh * ow;
+  for (int y = ty0 + ly; y < ty0 + tyn; y += 4) {
+    TO* o = out + (int64_t)b * 3 * plane + (int64_t)y * ow + xs;
+    if (aug_erased(it, y, xs)) {
+      st1<TO>(o, ev);
+      st1<TO>(o + plane, ev);
+      st1<TO>(o + 2 * plane, ev);
+      continue;
+    }
+    int v0, v1, v2;
+    if (fits) {
+      const int ylo = bh[2 * y], yn = bh[2 * y + 1];
+      const int* kh = kht + (int64_t)y * ks;
+      const uint32_t* col = hp + (ylo - r0) * TC + lx;
+      int acc0 = 1 << (PREC - 1), acc1 = acc0, acc2 = acc0;
+      for (int j = 0; j < yn; ++j) {
+        const uint32_t p = col[j * TC];
+        const int kv = kh[j];
+        acc0 += (int)(p & 255u) * kv;
+        acc1 += (int)((p >> 8) & 255u) * kv;
+        acc2 += (int)(p >> 16) * kv;
+      }
+      v0 = clip8(acc0);
+      v1 = clip8(acc1);
+      v2 = clip8(acc2);
+    } else {
+      resize_pixel(img, W, C, bw, bh, kwt, kht, ks, x, y, v0, v1, v2);
+    }
+    st1<TO>(o, val[v0]);
+    st1<TO>(o + plane, val[256 + v1]);
+    st1<TO>(o + 2 * plane, val[512 + v2]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Batch mix (vit_hip.h "Batch mix"): out[i] = x[src_i] inside image i's box, w_i * x[i] + (1 - w_i) * x[src_i] outside
 // it — mixup (empty box), CutMix (w = 1) and the unmixed image (w = 1, empty box) in one streaming kernel.
 // One lane owns U units of one image, a unit being 16 bytes of one row (VEC = 4 fp32 / 8 bf16 elements) or, where the
@@ -290,6 +504,62 @@ extern "C" int vit_resize_to_tensor(const void* src, const int64_t* meta, int64_
   else
     resize_apply_kernel<bf16_t><<<g2, 256, 0, s>>>((const uint8_t*)src, meta, oh, ow, ks, tab, (bf16_t*)out);
   return vit::check_launch("vit_resize_to_tensor");
+}
+
+extern "C" int64_t vit_augment_workspace_bytes(int64_t B, int64_t out_h, int64_t out_w, int64_t ksize) {
+  return vit_resize_workspace_bytes(B, out_h, out_w, ksize);       // the same tables, of the crops
+}
+
+extern "C" int vit_augment_to_tensor(const void* src, const int64_t* meta, const vit_aug_item* items_dev, int64_t B,
+                                     int64_t out_h, int64_t out_w, int64_t ksize, const float* mean3,
+                                     const float* std3, float erase_value, void* out, int32_t out_dtype,
+                                     void* workspace, int64_t workspace_bytes, void* stream) {
+  VIT_REQUIRE(src && meta && items_dev && out && workspace, "vit_augment_to_tensor: null pointer");
+  VIT_REQUIRE(B > 0 && out_h > 0 && out_w > 0 && ksize >= 3, "vit_augment_to_tensor: bad arguments");
+  VIT_REQUIRE(out_h <= 65535 && B <= 65535 && ksize <= 4096, "vit_augment_to_tensor: size out of range");
+  VIT_REQUIRE((mean3 == nullptr) == (std3 == nullptr), "vit_augment_to_tensor: mean3 and std3 go together");
+  AugNorm nm = {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, 0};
+  if (mean3) {
+    for (int c = 0; c < 3; ++c) {
+      VIT_REQUIRE(isfinite(mean3[c]) && isfinite(std3[c]) && std3[c] != 0.f,
+                  "vit_augment_to_tensor: mean must be finite and std finite and non-zero (channel %d: %g, %g)", c,
+                  (double)mean3[c], (double)std3[c]);
+      nm.mean[c] = mean3[c];
+      nm.sd[c] = std3[c];
+    }
+    nm.on = 1;
+  }
+  VIT_REQUIRE(isfinite(erase_value), "vit_augment_to_tensor: erase_value is not finite");
+  VIT_REQUIRE(out_dtype == VIT_F32 || out_dtype == VIT_BF16, "vit_augment_to_tensor: bad out dtype");
+  VIT_REQUIRE(workspace_bytes >= vit_augment_workspace_bytes(B, out_h, out_w, ksize),
+              "vit_augment_to_tensor: workspace too small");
+  hipStream_t s = VIT_STREAM(stream);
+  int* tab = (int*)workspace;
+  const int oh = (int)out_h, ow = (int)out_w, ks = (int)ksize;
+  const uint8_t* sp = (const uint8_t*)src;
+  dim3 g1((unsigned)((ow + oh + 255) / 256), (unsigned)B);
+  augment_coeffs_kernel<<<g1, 256, 0, s>>>(meta, items_dev, oh, ow, ks, tab);
+  const int64_t path = vit::opt(vit::OPT_AUGMENT_PATH);
+  const bool tiled = path == 2 || (path != 1 && ks <= AUG_TILED_MAX_KS);
+  if (tiled) {
+    dim3 g2((unsigned)((ow + VIT_AUG_TILE_COLS - 1) / VIT_AUG_TILE_COLS),
+            (unsigned)((oh + VIT_AUG_TILE_ROWS - 1) / VIT_AUG_TILE_ROWS), (unsigned)B);
+    if (out_dtype == VIT_F32)
+      augment_tiled_kernel<float><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value,
+                                                     (float*)out);
+    else
+      augment_tiled_kernel<bf16_t><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value,
+                                                      (bf16_t*)out);
+  } else {
+    dim3 g2((unsigned)((ow + 255) / 256), (unsigned)oh, (unsigned)B);
+    if (out_dtype == VIT_F32)
+      augment_apply_kernel<float><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value,
+                                                     (float*)out);
+    else
+      augment_apply_kernel<bf16_t><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value,
+                                                      (bf16_t*)out);
+  }
+  return vit::check_launch("vit_augment_to_tensor");
 }
 
 extern "C" int vit_mix_batch(const void* x, void* out, int32_t dtype, int64_t B, int64_t C, int64_t H, int64_t W,

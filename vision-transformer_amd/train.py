@@ -385,6 +385,19 @@ def main():
                     help="probability that a batch is mixed at all (with --mixup / --cutmix)")
     ap.add_argument("--mix-switch-prob", type=float, default=0.5, metavar="P",
                     help="probability of CutMix when both --mixup and --cutmix are on")
+    ap.add_argument("--random-resized-crop", action="store_true",
+                    help="train on a random crop of --crop-scale of the area and --crop-ratio aspect, resized to --img "
+                         "(torchvision's RandomResizedCrop; inside the resize launch on cuda; default: off)")
+    ap.add_argument("--crop-scale", type=float, nargs=2, default=(0.08, 1.0), metavar=("LO", "HI"))
+    ap.add_argument("--crop-ratio", type=float, nargs=2, default=(3 / 4, 4 / 3), metavar=("LO", "HI"))
+    ap.add_argument("--hflip", type=float, default=0.0, metavar="P",
+                    help="probability of a horizontal flip of a training image (default 0: off)")
+    ap.add_argument("--random-erase", type=float, default=0.0, metavar="P",
+                    help="probability of erasing a random box of a training image with 0 after the normalize (timm's "
+                         "RandomErasing, mode const; default 0: off)")
+    ap.add_argument("--mean", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="with --std: normalize training and test images per channel, (x - mean) / std")
+    ap.add_argument("--std", type=float, nargs=3, default=None, metavar=("R", "G", "B"))
     ap.add_argument("--reference-loop", action="store_true",
                     help="the reference's loop bookkeeping exactly: validate every epoch, restart the step counter on "
                          "resume, host-summed loss (train.py:60-119)")
@@ -426,6 +439,17 @@ def main():
     if args.mixup > 0 or args.cutmix > 0:
         from VisionTransformer.data import BatchMix
         mix = BatchMix(args.mixup, args.cutmix, prob=args.mix_prob, switch_prob=args.mix_switch_prob)
+    augmenting = args.random_resized_crop or args.hflip > 0 or args.random_erase > 0
+    if (args.mean is None) != (args.std is None):
+        ap.error("--mean and --std go together")
+    if args.data == "synthetic" and (augmenting or args.mean is not None):
+        ap.error("--random-resized-crop, --hflip, --random-erase, --mean and --std act in the image path, and "
+                 "--data synthetic feeds float tensors and has none: use --data synthetic-u8, cifar10-bin or folder")
+    augment = None
+    if augmenting:
+        from VisionTransformer.data import TrainAugment
+        augment = TrainAugment(scale=tuple(args.crop_scale) if args.random_resized_crop else None,
+                               ratio=tuple(args.crop_ratio), hflip=args.hflip, erase_prob=args.random_erase)
     if args.bench:
         steps = args.steps or 30
         sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm,
@@ -455,16 +479,20 @@ def main():
     if args.data != "synthetic" and device == "cuda":
         from VisionTransformer import data as D
         # one transform (and coefficient workspace) per loader: each stages its batches on its own side stream
+        # the augmentation is part of the resize launch, staged before the mix: erase precedes mixup, as in timm
+        train_tf = D.GpuTrainTransform(args.img, augment, mean=args.mean, std=args.std) if augment is not None \
+            else D.GpuImageTransform(args.img, mean=args.mean, std=args.std)
         train_loader = D.DeviceBatches(D.raw_loader(train_set, args.batch, shuffle=True, num_workers=args.workers,
-                                                    sampler=sampler), D.GpuImageTransform(args.img), device,
-                                      mix=mix)
+                                                    sampler=sampler), train_tf, device, mix=mix)
         test_loader = D.DeviceBatches(D.raw_loader(test_set, args.batch, shuffle=False, num_workers=args.workers,
-                                                   drop_last=False, sampler=tsampler), D.GpuImageTransform(args.img),
-                                      device)
+                                                   drop_last=False, sampler=tsampler),
+                                      D.GpuImageTransform(args.img, mean=args.mean, std=args.std), device)
     else:
         if args.data != "synthetic":
             from VisionTransformer import data as D
-            train_set, test_set = (D.Transformed(s, D.host_transform(args.img)) for s in (train_set, test_set))
+            plain = D.host_transform(args.img, mean=args.mean, std=args.std)
+            train_tf = D.host_train_transform(args.img, augment, args.mean, args.std) if augment is not None else plain
+            train_set, test_set = D.Transformed(train_set, train_tf), D.Transformed(test_set, plain)
         train_loader = torch.utils.data.DataLoader(train_set, batch_size=args.batch, shuffle=sampler is None,
                                                    sampler=sampler, num_workers=args.workers, drop_last=True,
                                                    pin_memory=pin)
