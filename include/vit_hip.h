@@ -78,7 +78,8 @@ const char* vit_last_error(void);
  * Since ABI 18, entry points that are purely added do not change the version: a host that needs one checks for the
  * symbol (dlsym, or a link error).  The version changes only when an existing signature or meaning does.  Added under
  * 18 this way: vit_softmax_xent_mixed and vit_mix_batch (label smoothing, mixup and CutMix), with no option name;
- * vit_augment_workspace_bytes and vit_augment_to_tensor (crop, flip, normalize, erase), with "augment_path".
+ * vit_augment_workspace_bytes and vit_augment_to_tensor (crop, flip, normalize, erase), with "augment_path";
+ * vit_drop_path_rows, vit_gemm_rowscale and vit_gemm_kernel_choice (stochastic depth), with no option name.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -145,6 +146,51 @@ int64_t vit_gemm_workspace_bytes(const vit_gemm_desc* d);
  * k-tiles deep.  Used for the weight-gradient GEMMs (reduction over B*T rows; transformer.py Linear backward). */
 int vit_gemm_split_k_hint(int64_t m, int64_t n, int64_t k, int in_dtype);
 int vit_gemm(const vit_gemm_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Stochastic depth (drop path; timm's drop_path with scale_by_keep=True — the reference has none): in training a
+ * whole residual branch is dropped per image, x = x + keep[b] / (1 - p_l) * dropout(branch(x)), keep ~ Bernoulli(1 -
+ * p_l) drawn per block l, site (0 = attention, 1 = FFN) and image b.  Two purely added entry points (ABI 18):
+ *
+ * vit_drop_path_rows: one launch fills the factor table of a whole forward, one float per token row,
+ *     out[(l*2 + site) * B*T + b*T + t] = keep ? 1.0f / (1.0f - rates[l]) : 0.0f      (L * 2 * B * T floats)
+ *     keep = vit_hash_u32(site_seed(seed, L + l, site), b) >= threshold(rates[l]),
+ *   with the counter hash, per-site seed and threshold of the element dropout (site_seed: the host package's and the
+ *   oracle's; layers L .. 2L-1 keep these streams apart from the element dropout's, which use 0 .. L-1).  `rates` is a
+ *   HOST float[L], copied into the kernel arguments: no table upload, no host sync, no allocation.  A rate of 0 gives
+ *   1.0f everywhere.  Refused: a NULL out / rates, L, B or T <= 0, L > VIT_DROP_PATH_MAX_LAYERS, B * T >= 2^31, a
+ *   rate outside [0, 1) or NaN.
+ *
+ * vit_gemm_rowscale: vit_gemm with one more epilogue step, after the dropout and before the residual add:
+ *     s = row_scale[(i + dropout_row0) * max(dropout_row_stride, 1)];   v = (s != 0) ? v * s : 0;
+ *   The row index is the dropout index's row, so a GEMM over a row range (dropout_row0) or over the token-0 rows
+ *   (dropout_row_stride = T) of a larger tensor addresses that tensor's table, which must reach that index for every
+ *   i < m.  The zero is a select, not a product: a dropped row passes on no inf or NaN of its branch.  mask_out is
+ *   vit_gemm's mask with the bits of every row whose s == 0 cleared, so the saved keep bits already combine both
+ *   masks and the backward needs the mask and the scalar 1 / ((1 - dropout_p)(1 - p_l)) alone.  Every kernel and
+ *   epilogue vit_gemm chooses between applies the factor (the 256x256 kernel through an epilogue kind of its own
+ *   beside the dropout + residual one, which is left as it was).  row_scale == NULL is vit_gemm itself; a table of
+ *   1.0f gives vit_gemm's bits.  row_scale is DEVICE memory, 4-B aligned.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define VIT_DROP_PATH_MAX_LAYERS 64
+int vit_drop_path_rows(float* out, uint32_t seed, int64_t L, int64_t B, int64_t T, const float* rates /* host, [L] */,
+                       void* stream);
+int vit_gemm_rowscale(const vit_gemm_desc* d, const float* row_scale /* device; NULL: vit_gemm */, void* stream);
+
+/* Which kernel vit_gemm (row_scale == NULL) or vit_gemm_rowscale would launch for this descriptor under the current
+ * options; nothing is launched and no pointer is read (added under ABI 18).  It is the launcher's own plan, so a test
+ * can tell that a case reaches the kernel it means to test.
+ *   *impl: 0 the fp32 kernel; 1 / 2 / 4 the bf16 kernel generation (option "gemm_impl")
+ *   *kind: the 256x256 kernel's epilogue kind (impl 4; VIT_EPI_GENERAL otherwise: the other kernels have the general
+ *          epilogue alone).  Named here: the kinds a dropout / residual epilogue can take.  Other values are further
+ *          fast kinds (bias + activation, ReLU masks, the patch embedding).
+ * Where a split-K tail follows the whole rounds of tiles, the whole-round launch is reported.  Refused: what vit_gemm
+ * refuses, and a NULL impl / kind. */
+#define VIT_EPI_BDR 3     /* dropout(alpha * acc [+ bias]) [+ residual], wide bf16 rows */
+#define VIT_EPI_SLAB 4    /* split-K fp32 slabs; the reduce then runs the general epilogue */
+#define VIT_EPI_GENERAL 5 /* the general epilogue */
+#define VIT_EPI_BDRS 8    /* VIT_EPI_BDR with the row factor of vit_gemm_rowscale */
+int vit_gemm_kernel_choice(const vit_gemm_desc* d, const float* row_scale, int32_t* impl, int32_t* kind);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Patch embedding (vit.py:21-29,39-42).

@@ -52,17 +52,30 @@ def patch_embed(x, w, b, cls, pos, P):
     return torch.cat([e, cls.to(e.dtype)], dim=1) + pos
 
 
-def block(blk, x, training, want_probs=False):
-    """Pre-LN block (transformer.py:76-79): x + drop(proj(MHA(ln1 x))), then x + drop(FFN(ln2 x))."""
+def drop_path(y, p, training):
+    """Stochastic depth of a [B, T, D] branch output (timm's drop_path, scale_by_keep=True): image b's slab is kept
+    and scaled by 1 / (1 - p) with probability 1 - p, else zeroed — one torch.rand(B, 1, 1) draw per call.  With
+    p == 0 or outside training it returns y and draws nothing, so the CPU RNG stream (hence the dropout masks) of a
+    rate-0 model is the one it always was."""
+    if p == 0.0 or not training:
+        return y
+    keep = torch.rand(y.shape[0], 1, 1, device=y.device) >= p
+    return (y / (1.0 - p)) * keep.to(y.dtype)
+
+
+def block(blk, x, training, want_probs=False, drop_path_rate=0.0):
+    """Pre-LN block (transformer.py:76-79): x + drop(proj(MHA(ln1 x))), then x + drop(FFN(ln2 x)); each branch
+    under drop_path(., drop_path_rate)."""
     mh = blk.multi_head
     a = F.layer_norm(x, (x.shape[-1],), blk.ln1.weight, blk.ln1.bias, LN_EPS)
     o, probs = attention(a, _fused_qkv_weight(mh), len(mh.heads), want_probs)
     mh.attention_probs = probs.detach() if probs is not None else None
-    x = x + F.dropout(F.linear(o, mh.proj.weight, mh.proj.bias), DROPOUT_P, training)
+    x = x + drop_path(F.dropout(F.linear(o, mh.proj.weight, mh.proj.bias), DROPOUT_P, training), drop_path_rate,
+                      training)
     fc1, _, fc2, _ = blk.ffwd.mlp
     a = F.layer_norm(x, (x.shape[-1],), blk.ln2.weight, blk.ln2.bias, LN_EPS)
     h = torch.relu(F.linear(a, fc1.weight, fc1.bias))
-    return x + F.dropout(F.linear(h, fc2.weight, fc2.bias), DROPOUT_P, training)
+    return x + drop_path(F.dropout(F.linear(h, fc2.weight, fc2.bias), DROPOUT_P, training), drop_path_rate, training)
 
 
 def vit_forward(model, x):
@@ -73,8 +86,9 @@ def vit_forward(model, x):
         raise RuntimeError(f"batch size {x.shape[0]} != config.batch_size {emb.cls_tkn_embd.shape[0]} "
                            "(the CLS token parameter is batch-shaped)")
     e = patch_embed(x, conv.weight, conv.bias, emb.cls_tkn_embd, emb.pos_embd, conv.kernel_size[0])
-    for blk in model.transformer_encoder.blocks:
-        e = block(blk, e, model.training, model.wants_attention_probs(x.shape[0]))
+    rates = model.drop_path_rates
+    for l, blk in enumerate(model.transformer_encoder.blocks):
+        e = block(blk, e, model.training, model.wants_attention_probs(x.shape[0]), rates[l])
     fc0, _, ln, fc3 = model.mlp
     z = F.gelu(F.linear(e[:, 0, :], fc0.weight, fc0.bias))                  # token 0 = first PATCH (vit.py:80)
     z = F.layer_norm(z, (z.shape[-1],), ln.weight, ln.bias, LN_EPS)

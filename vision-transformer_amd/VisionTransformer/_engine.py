@@ -19,6 +19,7 @@ Layouts (device):
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import math
 import weakref
 from typing import NamedTuple, Optional
@@ -94,6 +95,25 @@ def dropout_seed(base_seed, rank=0):
     return _hash_u32((base_seed ^ 0x5BD1E995) & 0xFFFFFFFF, 0x27D4EB2F + rank) & 0x7FFFFFFF
 
 
+def path_keep(base_seed, L, layer, site, B, p):
+    """Python twin of the drop-path draw of vit_drop_path_rows: bool [B], image b keeps the branch of (layer, site)
+    iff vit_hash_u32(site_seed(base_seed, L + layer, site), b) >= threshold(p).  `base_seed`: the forward's seed after
+    dropout_seed; layers L .. 2L-1 keep these streams apart from the element dropout's (0 .. L-1).  The threshold is
+    the library's: of p as the fp32 value it receives."""
+    thr = min(int(ctypes.c_float(p).value * 4294967296.0), 0xFFFFFFFF)
+    s = site_seed(base_seed, L + layer, site)
+    return torch.tensor([_hash_u32(s, b) >= thr for b in range(B)], dtype=torch.bool)
+
+
+def _keep_scale(p):
+    """(the element dropout's p folded with a block's drop-path rate, its 1 / keep probability): what the backward's
+    consumers of a bare-masked gradient apply.  Rate 0 gives DROPOUT_P and 1 / (1 - DROPOUT_P) as they always were."""
+    if p == 0.0:
+        return DROPOUT_P, 1.0 / (1.0 - DROPOUT_P)
+    keep = (1.0 - DROPOUT_P) * (1.0 - p)
+    return 1.0 - keep, 1.0 / keep
+
+
 class _Region:
     def __init__(self):
         self.size = 0
@@ -124,7 +144,7 @@ def head_split_for(m, n, k):
 class Tape:
     """Activations saved by a training forward (`blocks`: one BlockActs per encoder block)."""
     __slots__ = ("B", "cols", "blocks", "z", "u", "gz", "zn", "mh", "rh", "seed", "training", "x_shape", "x_dtype",
-                 "x_grad", "pruned", "row0")
+                 "x_grad", "pruned", "row0", "path_rates")
 
 
 # per-block gradient regions, in their order in the flat gradient buffer (qkv_w: the fused [3D, D] matrix of every head)
@@ -535,6 +555,14 @@ class Engine:
         prm = self.params
         seed = dropout_seed(int(torch.randint(0, 2 ** 31 - 1, (1,)).item()), self.dropout_rank) if training else 0
         tape = Tape() if save else None
+        # Stochastic depth (model.drop_path_rates, training only): one launch fills the per-row factor table of every
+        # (block, site) — 1 / (1 - p_l) on the rows of the images that keep the branch, 0 on the others — which the
+        # proj / fc2 GEMMs of the blocks with p_l > 0 apply in their epilogue (vit_gemm_rowscale).  All rates 0: no
+        # table, and every launch is the one it always was.
+        rates = [float(p) for p in self.model_ref().drop_path_rates] if training else []
+        path = _ops.drop_path_rows(seed, rates, B, T, x.device) if any(rates) else None
+        # block l's [2, B*T] slice of the table, None where its rate is 0
+        paths = [path[l] if path is not None and rates[l] > 0.0 else None for l in range(L)]
 
         blocks = []
         # The classifier reads token 0 of the last block's output only (vit.py:80), and everything after the last
@@ -547,12 +575,13 @@ class Engine:
         xcur = torch.empty(B * T, D, dtype=dt, device=x.device)
         if (nc > 1 and not want_probs and self.profile_hook is None and B % (4 * nc) == 0
                 and ((B // nc) * T) % 4 == 0):
-            xcur = self._forward_blocks_split(x, cols, xcur, B, training, seed, save, prune, blocks, nc)
+            xcur = self._forward_blocks_split(x, cols, xcur, B, training, seed, save, prune, blocks, nc,
+                                              paths=paths)
         else:
             self._embed(x, cols, xcur, 0, B)
             for l in range(L):
                 xcur, saved = self.block_forward(l, xcur, B, training, seed, save, want_probs,
-                                                 pr=prune and l == L - 1)
+                                                 pr=prune and l == L - 1, path_scale=paths[l])
                 if save:
                     blocks.append(saved)
         # classifier on token 0 (= first PATCH, vit.py:80): Linear -> GELU(erf) -> LayerNorm(4D) -> Linear, fp32
@@ -570,6 +599,9 @@ class Engine:
             # which attention the pruned block's forward ran (query 0 alone, or the full kernels): its backward must
             # be the matching one whatever row0_attention says by then (the row-0 forward writes only rows b*T)
             tape.row0 = prune and self.row0_attention and not want_probs
+            # ... and the drop-path rates its keep bits were drawn with: the backward's scalars follow the forward,
+            # whatever model.drop_path_rates says by then
+            tape.path_rates = rates if path is not None else None
         return logits, tape
 
     def _block_bufs(self, x_in, B, training, save, pr=False, q0only=False):
@@ -609,13 +641,15 @@ class Engine:
         self._mark("gemm_fwd", 1)
         _ops.embed_cls(prm["cls"].reshape(-1, D)[b0:b0 + B], prm["pos"], xc, B, T, D)  # CLS appended LAST
 
-    def _forward_blocks_split(self, x, cols, xcur, B, training, seed, save, prune, blocks, nc=2):
+    def _forward_blocks_split(self, x, cols, xcur, B, training, seed, save, prune, blocks, nc=2, *, paths=None):
         """The patch embedding and the encoder blocks as nc chains of B/nc images on nc HIP streams (default two),
         into the whole-batch cols / xcur allocated on the current stream, up to the last block's output, which the
         current stream then waits for.  Every kernel is the one-chain forward's on a row range (rows are
         independent; dropout indices are the whole batch's), so the outputs are bitwise the same; the chains fill
         each other's idle CUs.  The blocks' outputs are whole-batch buffers allocated on the current stream and
-        recorded on every chain stream."""
+        recorded on every chain stream.  `paths`: per block, its slice of the drop-path factor table (forward) or
+        None; a chain's GEMMs read the whole batch's slice at their rows."""
+        paths = paths if paths is not None else [None] * self.L
         T, L = self.T, self.L
         dev = xcur.device
         cur = torch.cuda.current_stream(dev)
@@ -632,7 +666,7 @@ class Engine:
                     for st in streams:
                         t.record_stream(st)
 
-        on_chains((x, cols, xcur))
+        on_chains((x, cols, xcur, *paths))         # (views of one table: each records its storage)
         for i, st in enumerate(streams):
             with torch.cuda.stream(st):
                 self._embed(x, cols, xcur, i * Bh, Bh)
@@ -664,7 +698,7 @@ class Engine:
                 with torch.cuda.stream(st):
                     part = acts.images(i * Bh, Bh, T)
                     self.block_forward(l, part.x_in, Bh, training, seed, save, out=(part, x_out[i * Mh:(i + 1) * Mh]),
-                                       row0=i * Mh, attn_wgs=wgs)
+                                       row0=i * Mh, attn_wgs=wgs, path_scale=paths[l])
             if save:
                 blocks.append(acts)
             xcur = x_out
@@ -683,23 +717,27 @@ class Engine:
         if nsplit < L:
             if not q0only:
                 self._ln1_qkv(L - 1, *whole, False)
-            xcur = self._attend_ffn(L - 1, acts, x_out, B, training, seed, save, False, True, q0only)
+            xcur = self._attend_ffn(L - 1, acts, x_out, B, training, seed, save, False, True, q0only,
+                                    path_scale=paths[L - 1])
             if save:
                 blocks.append(acts)
         return xcur
 
     def block_forward(self, l, x_in, B, training, seed, save, want_probs=False, *, pr=False, out=None, row0=0,
-                      attn_wgs=0):
+                      attn_wgs=0, path_scale=None):
         """Block l (transformer.py:76-79) on x_in [B*T, D] (compute dtype): x_mid = x_in + drop(MHA(ln1(x_in))),
         x_out = x_mid + drop(FFN(ln2(x_mid))).  `pr`: the post-attention part on the B token-0 rows only (the pruned
         last block).  Returns (x_out, saved): `saved` is the BlockActs block_backward needs (None unless `save`).
         `out` (the two-stream forward, _forward_blocks_split): the (BlockActs, x_out) to write into instead of fresh
         ones — a row range (BlockActs.images) of the whole batch's, x_in being its row `row0`: the dropout bits are
-        drawn at the whole batch's indices."""
+        drawn at the whole batch's indices.  `path_scale` (drop path): this block's [2, rows] slice of the whole
+        batch's factor table (_ops.drop_path_rows), site 0 for the attention branch and 1 for the FFN's, read at the
+        dropout's row indices; None: no drop path."""
         q0only = pr and self.row0_attention and not want_probs  # the pruned block's attention on query 0 alone
         a, x_out = out if out is not None else self._block_bufs(x_in, B, training, save, pr, q0only)
         self._ln1_qkv(l, a.x_in, a.a1, a.m1, a.r1, a.qkv, q0only)
-        self._attend_ffn(l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0, attn_wgs)
+        self._attend_ffn(l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0, attn_wgs,
+                         path_scale=path_scale)
         return x_out, a if save else None
 
     def _ln1_qkv(self, l, x_in, a1, m1, r1, qkv, kv_only):
@@ -723,7 +761,8 @@ class Engine:
             _ops.gemm(a1, wq, qkv, M, 3 * D, D, D, D, 3 * D)
         mk("gemm_fwd", 1)
 
-    def _attend_ffn(self, l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0=0, attn_wgs=0):
+    def _attend_ffn(self, l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0=0, attn_wgs=0, *,
+                    path_scale=None):
         """The rest of block l's forward from _ln1_qkv's a.a1 / a.qkv: attention, proj + residual, ln2, FFN +
         residual into x_out (arguments as block_forward's); returns x_out."""
         D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
@@ -762,7 +801,8 @@ class Engine:
         mk("gemm_fwd", 0, 2.0 * R * D * D, (3 * R * D + D * D) * es)
         self._gemm_rows(pr, a.o, self.ww[f"{l}.proj_w"], a.x_mid, R, D, D, rs * D, D, D, bias=prm[f"{l}.proj_b"],
                         res=a.x_in, ldres=rs * D, dropout_p=drop_p, seed=site_seed(seed, l, 0),
-                        drop_row_stride=rs, mask_out=a.pm, drop_row0=row0)
+                        drop_row_stride=rs, mask_out=a.pm, drop_row0=row0,
+                        row_scale=None if path_scale is None else path_scale[0])
         mk("gemm_fwd", 1)
         mk("ln_fwd", 0, 0.0, 2 * R * D * es + 8 * R)
         _ops.layernorm_fwd(a.x_mid, prm[f"{l}.ln2_w"], prm[f"{l}.ln2_b"], eps=LN_EPS, y=a.a2, mean=a.m2, rstd=a.r2)
@@ -776,7 +816,7 @@ class Engine:
         mk("gemm_fwd", 0, 2.0 * R * 4 * D * D, (4 * R * D + 4 * D * D + 2 * R * D) * es)
         self._gemm_rows(pr, a.h, self.ww[f"{l}.fc2_w"], x_out, R, D, 4 * D, 4 * D, 4 * D, D, bias=prm[f"{l}.fc2_b"],
                         res=a.x_mid, ldres=D, dropout_p=drop_p, seed=site_seed(seed, l, 1), drop_row_stride=rs,
-                        mask_out=a.fm, drop_row0=row0)
+                        mask_out=a.fm, drop_row0=row0, row_scale=None if path_scale is None else path_scale[1])
         mk("gemm_fwd", 1)
         return x_out
 
@@ -911,13 +951,17 @@ class Engine:
         else:
             g1 = dx
         g1_summed = False          # block L-1's fc2 bias gradient: g1 comes from the head (plain column sum below)
+        # drop path: the saved keep bits already hold "element kept and the image's branch kept", so the backward
+        # differs only in the scalar 1 / ((1 - p_drop)(1 - p_l)) of each block, from the forward's own rates
+        rates = tape.path_rates or [0.0] * L
         for l in reversed(range(L)):
             if not need_from[l]:
                 break
             prev_mask = tape.blocks[l - 1].fm if (tape.training and l > 0) else None
             dx, g1n = self.block_backward(l, tape.blocks[l], dx, g1, g1_summed, beta, req, side, tape.training, B,
                                           pruned and l == L - 1, chain_prev=l > 0, prev_mask=prev_mask,
-                                          row0=tape.row0 and l == L - 1)
+                                          row0=tape.row0 and l == L - 1, path_rate=rates[l],
+                                          prev_path_rate=rates[l - 1] if l > 0 else 0.0)
             g1_summed = l > 0
             self._bucket_ready(self.block_range[l], side)
             g1 = g1n if g1n is not None else dx
@@ -949,7 +993,7 @@ class Engine:
         return dimg
 
     def block_backward(self, l, acts, dx, g1, g1_summed, beta, req, side, training, B, pr=False, chain_prev=False,
-                       prev_mask=None, row0=None):
+                       prev_mask=None, row0=None, *, path_rate=0.0, prev_path_rate=0.0):
         """Backward of block l (`acts`: its forward's BlockActs) from d(x_out) = dx and g1 = the fc2-dropout-masked dx
         (dx itself in eval).  Writes the block's weight gradients into the flat buffer (beta: 0 overwrite / 1
         accumulate; req: which regions want a gradient) and returns (dx_in, g1n).  `chain_prev`: there is a block l-1
@@ -957,7 +1001,9 @@ class Engine:
         keep bits `prev_mask` — g1n, the next block's masked gradient (None otherwise).  `g1_summed`: this block's fc2
         bias gradient was already summed by the block above.  `pr`: the pruned last block (dx / g1 are its B token-0
         rows).  `row0`: its forward ran the query-0 attention (Tape.row0; None: pr and self.row0_attention, for
-        direct callers)."""
+        direct callers).  `path_rate` / `prev_path_rate`: the drop-path rates the forward of this block / of block
+        l-1 ran with (Tape.path_rates): they enter only the 1 / keep-probability scalars of the masked gradients'
+        consumers, the masks themselves being the forward's combined keep bits."""
         if row0 is None:
             row0 = pr and self.row0_attention
         D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
@@ -967,7 +1013,8 @@ class Engine:
         es = 2 if dt == torch.bfloat16 else 4
         mk = self._mark
         dev = dx.device
-        gs = 1.0 / (1.0 - DROPOUT_P) if training else 1.0
+        drop_p, gs = _keep_scale(path_rate) if training else (DROPOUT_P, 1.0)
+        prev_drop_p = _keep_scale(prev_path_rate)[0] if training else DROPOUT_P
         R, rs = (B, T) if pr else (M, 1)
         # FFN: x_out = x_mid + drop(relu(ln2(x_mid) W1^T + b1) W2^T + b2)
         if req[f"{l}.fc2_w"]:
@@ -995,7 +1042,7 @@ class Engine:
         # sums of g0 as stored = the proj bias gradient
         mk("ln_bwd", 0, 0.0, (3 + 1 + (g0 is not None)) * R * D * es + 8 * R + R * D // 8)
         part = _ops.layernorm_bwd(da2, acts.x_mid, prm[f"{l}.ln2_w"], acts.m2, acts.r2, dx_mid, dres=dx, drop_out=g0,
-                                  drop_p=DROPOUT_P, drop_mask=acts.pm, osum=True)
+                                  drop_p=drop_p, drop_mask=acts.pm, osum=True)
         mk("ln_bwd", 1)
         cs_jobs.append((part, [gw[f"{l}.ln2_w"], gw[f"{l}.ln2_b"], gw[f"{l}.proj_b"]], beta))
         if g0 is None:
@@ -1068,7 +1115,7 @@ class Engine:
         # = the fc2 bias gradient of block l-1
         mk("ln_bwd", 0, 0.0, (3 + 1 + (g1n is not None)) * M * D * es + 8 * M)
         part = _ops.layernorm_bwd(da1, acts.x_in, prm[f"{l}.ln1_w"], acts.m1, acts.r1, dx_in, dres=dx_mid, drop_out=g1n,
-                                  drop_p=DROPOUT_P, drop_mask=prev_mask if g1n is not None else None,
+                                  drop_p=prev_drop_p, drop_mask=prev_mask if g1n is not None else None,
                                   osum=chain_prev)
         mk("ln_bwd", 1)
         outs = [gw[f"{l}.ln1_w"], gw[f"{l}.ln1_b"]] + ([gw[f"{l - 1}.fc2_b"]] if chain_prev else [])

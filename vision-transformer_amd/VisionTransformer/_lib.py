@@ -114,7 +114,15 @@ _SIGS = {
     "vit_mix_batch": (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _I64, _I64, _P, _P]),
     "vit_augment_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "vit_augment_to_tensor": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _F, _P, _I32, _P, _I64, _P]),
+    "vit_drop_path_rows": (ctypes.c_int, [_P, _U32, _I64, _I64, _I64, ctypes.POINTER(ctypes.c_float), _P]),
+    "vit_gemm_rowscale": (ctypes.c_int, [ctypes.POINTER(GemmDesc), _P, _P]),
+    "vit_gemm_kernel_choice": (ctypes.c_int, [ctypes.POINTER(GemmDesc), _P, ctypes.POINTER(_I32),
+                                              ctypes.POINTER(_I32)]),
 }
+
+EPI_BDR, EPI_SLAB, EPI_GENERAL, EPI_BDRS = 3, 4, 5, 8    # VIT_EPI_* (vit_hip.h): kinds vit_gemm_kernel_choice reports
+
+DROP_PATH_MAX_LAYERS = 64    # VIT_DROP_PATH_MAX_LAYERS (vit_hip.h)
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 

@@ -44,18 +44,30 @@ def mask4_empty(m, n, device):
     return torch.empty(mask4_bytes(m, n), dtype=torch.uint8, device=device)
 
 
+# None, or a list: every gemm() then appends what the library says it launches for the call (vit_gemm_kernel_choice:
+# the kernel generation and the 256x256 kernel's epilogue kind, _lib.EPI_*), so a test can tell which kernel a case —
+# the engine's own launches included — really reached.  Off (None) it costs one comparison.
+GEMM_CHOICE_LOG = None
+
+
 def gemm(a, b, c, m, n, k, lda, ldb, ldc, a_kcontig=True, b_kcontig=True, alpha=1.0, beta=0.0, bias=None,
          act=ACT_NONE, aux=None, ldaux=0, res=None, ldres=0, res_rowmod=0, dropout_p=0.0, seed=0, split_k=1,
          out_group=(0, 0), workspace=None, colsum_part=None, mask_out=None, drop_row_stride=1, shared_cus=False,
-         drop_row0=0, stream=None):
+         drop_row0=0, row_scale=None, stream=None):
     """C[i][j] = epi(alpha * sum_r A(i,r) B(j,r)); see include/vit_hip.h.  `shared_cus`: VIT_FLAG_SHARED_CUS (other
     kernels — RCCL collectives — may hold CUs meanwhile: no persistent grid).  `colsum_part` (f32, colsum_part_rows(m) x n)
     receives per-256-row-block column sums of C as stored — finish with colsum_finish.  `aux` may be a uint8 mask4
     tensor (the ReLU mask saved by the forward); `mask_out` (uint8, mask4_bytes(m, n)) receives C's mask4 (dropout
     keep bits when dropout_p > 0, else C > 0).  `drop_row_stride` S: output row i draws the dropout bits of row i*S of
     the full tensor (C = token-0 rows of it); `drop_row0` R0: row i draws those of row i + R0 (C = a row range of a
-    larger tensor).  Returns c."""
-    _need_cuda(a, b, c, bias, aux, res, colsum_part, mask_out)
+    larger tensor).  `row_scale` (f32, vit_gemm_rowscale): a per-row factor applied after the dropout, read at that same
+    row index (i + R0) * S — 0 drops the row's branch and clears its mask_out bits (drop path).  Returns c."""
+    _need_cuda(a, b, c, bias, aux, res, colsum_part, mask_out, row_scale)
+    if row_scale is not None:
+        if row_scale.dtype != torch.float32 or not row_scale.is_contiguous():
+            raise TypeError("gemm: row_scale must be contiguous float32")
+        if row_scale.numel() <= (m - 1 + drop_row0) * max(drop_row_stride, 1):
+            raise ValueError("gemm: row_scale does not reach the last row's index")
     if a.dtype != b.dtype:
         raise TypeError("gemm: A and B dtypes differ")
     if bias is not None and bias.dtype != torch.float32:
@@ -100,8 +112,32 @@ def gemm(a, b, c, m, n, k, lda, ldb, ldc, a_kcontig=True, b_kcontig=True, alpha=
             if stream is not None:
                 workspace.record_stream(stream)      # freed on return: not reusable before `stream` is done with it
         d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    if GEMM_CHOICE_LOG is not None:
+        impl, kind = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.load().vit_gemm_kernel_choice(ctypes.byref(d), _ptr(row_scale), ctypes.byref(impl),
+                                                      ctypes.byref(kind)), "vit_gemm_kernel_choice")
+        GEMM_CHOICE_LOG.append({"m": m, "n": n, "k": k, "row_scale": row_scale is not None, "impl": impl.value,
+                                "kind": kind.value})
+    if row_scale is not None:
+        _lib.check(_lib.load().vit_gemm_rowscale(ctypes.byref(d), _ptr(row_scale), _stream(stream)),
+                   "vit_gemm_rowscale")
+        return c
     _lib.check(_lib.load().vit_gemm(ctypes.byref(d), _stream(stream)), "vit_gemm")
     return c
+
+
+def drop_path_rows(seed, rates, B, T, device, out=None, stream=None):
+    """The drop-path factor table of one forward (vit_drop_path_rows): float32 [L, 2, B*T], entry (l, site, b*T + t) =
+    1 / (1 - rates[l]) where image b keeps its (l, site) branch, else 0.  `rates`: L host floats, passed in the kernel
+    arguments (no upload, no sync)."""
+    L = len(rates)
+    if L > _lib.DROP_PATH_MAX_LAYERS:
+        raise ValueError(f"drop_path_rows: {L} layers exceed the library's {_lib.DROP_PATH_MAX_LAYERS}")
+    out = torch.empty(L, 2, B * T, dtype=torch.float32, device=device) if out is None else out
+    _need_cuda(out)
+    arr = (ctypes.c_float * L)(*rates)
+    _lib.call("vit_drop_path_rows", _ptr(out), seed & 0xFFFFFFFF, L, B, T, arr, _stream(stream))
+    return out
 
 
 def colsum_part_rows(m):

@@ -7,7 +7,12 @@ Differences, all optional / additive:
     (optimizer state is fp32) and `precision` selects the arithmetic of the whole network.
   * `dropout` is stored and, like the reference, not used: dropout is p = 0.2 at the two sites per block
     (transformer.py:35,53).
+  * `drop_path_rate` (new, keyword-only, default 0): stochastic depth.  Block l of L drops each of its two residual
+    branches per image with rate `drop_path_rates(rate, L)[l]` — timm's linear rule, 0 for the first block, `rate`
+    for the last — in training mode only; 0 is exactly the model without the keyword.
 """
+import math
+
 import torch
 
 PRESETS = {
@@ -19,9 +24,24 @@ PRESETS = {
 }
 
 
+def check_drop_path_rate(p, what="drop_path_rate"):
+    """`p` as a float in [0, 1), or ValueError / TypeError."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)):
+        raise TypeError(f"{what} must be a number, got {type(p).__name__}")
+    p = float(p)
+    if not (math.isfinite(p) and 0.0 <= p < 1.0):
+        raise ValueError(f"{what} must lie in [0, 1), got {p}")
+    return p
+
+
+def drop_path_rates(rate, num_blocks):
+    """Per-block rates, timm's rule: [x.item() for x in torch.linspace(0, rate, num_blocks)]."""
+    return [x.item() for x in torch.linspace(0, check_drop_path_rate(rate), num_blocks)]
+
+
 class ViTConfig:
     def __init__(self, input_channels, num_classes, num_patches, embedding_size, patch_size, num_heads, num_blocks,
-                 device, batch_size, dropout=0.2, precision=torch.float32, *, compute_dtype=None):
+                 device, batch_size, dropout=0.2, precision=torch.float32, *, compute_dtype=None, drop_path_rate=0.0):
         self.input_channels = input_channels
         self.num_classes = num_classes
         self.num_patches = num_patches
@@ -38,6 +58,7 @@ class ViTConfig:
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"compute_dtype must be torch.float32 or torch.bfloat16, got {compute_dtype}")
         self.compute_dtype = compute_dtype
+        self.drop_path_rate = check_drop_path_rate(drop_path_rate)
 
     @classmethod
     def preset(cls, name, img_size=224, patch_size=16, num_classes=1000, batch_size=256, device="cuda",

@@ -5,7 +5,9 @@ Constructor signatures, sub-module names and parameter registration order are th
 reference in tests/test_dropin_cpu.py).  The arithmetic is not torch's: every forward here runs libvit_hip kernels
 (module-level path, `_functional.py`) on ROCm tensors; on CPU tensors they run the host path (`_cpu.py`,
 train.py --device cpu).  `VisionTransformer.forward` does not call these forwards at all — it runs
-the fused whole-model engine (`_engine.py`) over the same parameters.
+the fused whole-model engine (`_engine.py`) over the same parameters.  Stochastic depth (`model.drop_path_rates`,
+`ViTConfig(drop_path_rate=...)`) lives in that whole-model forward (and the host path's) only: a `Block.forward` called
+directly is the reference's block, without drop path.
 
 Reference semantics kept:
   * Head: separate key/query/value projections without bias; logits MULTIPLIED by sqrt(head_size); returns

@@ -39,6 +39,13 @@ Extra (additive) API:
     the optimizer's launch, and its `ema_weights()` swaps it in and out of this model's own buffers, shadows included
     (optim.py).  `AveragedModel` still works, with the `repack()` above.
 
+  * `model.drop_path_rates` — stochastic depth: a list of one rate per encoder block, built from
+    `ViTConfig(drop_path_rate=...)` by timm's linspace rule and settable (a list of `num_blocks` numbers in [0, 1)).
+    In training mode each block drops each of its two residual branches per image with its rate and scales the
+    kept ones by 1 / (1 - rate) (timm's `drop_path`, scale_by_keep=True), inside the proj / fc2 GEMM epilogues; in
+    eval mode and at rate 0 nothing changes.  Plain attributes, no parameter or buffer: `state_dict()` and
+    checkpoints are unchanged.
+
 Device semantics (the reference picks 'cuda' or 'cpu', train.py:26): a model on a ROCm device runs the fused HIP
 engine and fails loudly when libvit_hip.so is missing; a model on the CPU runs the host path `_cpu.py` (plain torch
 ops, standard autograd).  A CUDA input never falls back to the host path.
@@ -114,6 +121,7 @@ class VisionTransformer(nn.Module):
             nn.Linear(4 * config.embedding_size, config.num_classes),
         )
         self.store_attention_probs = None        # auto (module docstring); True / False force it
+        self.drop_path_rates = _config.drop_path_rates(getattr(config, "drop_path_rate", 0.0), config.num_blocks)
         self._engine = None
         self._anchor = None
 
@@ -135,6 +143,21 @@ class VisionTransformer(nn.Module):
     @vit_config.setter
     def vit_config(self, config):
         self.__dict__["_vit_config"] = config
+
+    @property
+    def drop_path_rates(self):
+        """Stochastic-depth rate of every encoder block (module docstring), as a copy: assign a whole list of
+        num_blocks rates to change them, so that every entry is validated."""
+        rates = self.__dict__.get("_drop_path_rates")        # (None: a model pickled before the attribute)
+        return list(rates) if rates is not None else [0.0] * self.vit_config.num_blocks
+
+    @drop_path_rates.setter
+    def drop_path_rates(self, rates):
+        rates = [_config.check_drop_path_rate(p, f"drop_path_rates[{i}]") for i, p in enumerate(rates)]
+        n = self.vit_config.num_blocks
+        if len(rates) != n:
+            raise ValueError(f"drop_path_rates needs one rate per encoder block ({n}), got {len(rates)}")
+        self.__dict__["_drop_path_rates"] = rates
 
     @property
     def hip_engine(self):

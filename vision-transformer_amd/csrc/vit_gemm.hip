@@ -38,6 +38,7 @@ struct EpiParams {
   int64_t row0;    // global row of local row 0 (split-K tail launch): dropout indices use the global row
   uint8_t* mask_out;  // mask4 of C: dropout keep bits, else (C as stored > 0) — see vit_hip.h
   int64_t drop_rs;    // dropout index row = (i + row0) * drop_rs (rows of a row-strided view keep their global index)
+  const float* row_scale;  // vit_gemm_rowscale: per-row factor at that same row index (drop path), else null
 };
 
 
@@ -110,6 +111,13 @@ VIT_DEV void epilogue4(const EpiParams& e, int64_t i, int64_t j, float v[4]) {
         v[r] = k ? v[r] * e.drop_scale : 0.f;
       }
     }
+    bool rowon = true;
+    if (e.row_scale) {                                  // a select, not a product: a dropped row passes no inf / NaN on
+      const float s = e.row_scale[(i + e.row0) * e.drop_rs];
+      rowon = s != 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = rowon ? v[r] * s : 0.f;
+    }
     if (e.res) {
       float a[4];
       if (e.res_dtype == VIT_BF16) ld4<bf16_t>((const bf16_t*)e.res + rrow * e.ldres + j, a);
@@ -122,10 +130,11 @@ VIT_DEV void epilogue4(const EpiParams& e, int64_t i, int64_t j, float v[4]) {
       uint32_t bits = 0u;
 #pragma unroll
       for (int r = 0; r < 4; ++r) bits |= (uint32_t)(sizeof(TO) == 2 ? bf2f(f2bf(v[r])) > 0.f : v[r] > 0.f) << r;
-      e.mask_out[mask4_byte(i, j, e.n)] = (uint8_t)(e.use_drop ? keep : bits);
+      e.mask_out[mask4_byte(i, j, e.n)] = (uint8_t)(rowon ? (e.use_drop ? keep : bits) : 0u);
     }
   } else {
     uint32_t mbits = 0u;
+    const float s = e.row_scale ? e.row_scale[(i + e.row0) * e.drop_rs] : 1.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t jj = j + r;
@@ -145,10 +154,11 @@ VIT_DEV void epilogue4(const EpiParams& e, int64_t i, int64_t j, float v[4]) {
         k = vit_hash_u32(e.seed, (uint32_t)((i + e.row0) * e.drop_rs * e.n + jj)) >= e.drop_thr;
         x = k ? x * e.drop_scale : 0.f;
       }
+      if (e.row_scale) x = s != 0.f ? x * s : 0.f;
       if (e.res) x += ld_any(e.res, e.res_dtype, rrow * e.ldres + jj);
       st1<TO>(cp + r, x);
       const float stored = ld1<TO>(cp + r);
-      mbits |= (uint32_t)(e.use_drop ? k : stored > 0.f) << ((jj & 3));
+      mbits |= (uint32_t)(s != 0.f && (e.use_drop ? k : stored > 0.f)) << ((jj & 3));
     }
     if (e.mask_out) {                                   // j % 4 == 0 here: the row's 4-column group is one byte
       e.mask_out[mask4_byte(i, j, e.n)] = (uint8_t)mbits;
@@ -520,8 +530,10 @@ enum EpiKind : int {
   EPI_SLAB = 4,       // split-K fp32 slab
   EPI_GENERAL = 5,    // epilogue4 (beta, row groups, row-modulo residual, unaligned, any combination)
   EPI_AUXM = 6,       // alpha * acc masked by a mask4 bit (ReLU backward from the forward's stored mask)
-  EPI_PATCH = 7       // alpha * acc + bias + res_f32[i % res_rowmod] stored at row (i / G) * Gs + i % G: the
+  EPI_PATCH = 7,      // alpha * acc + bias + res_f32[i % res_rowmod] stored at row (i / G) * Gs + i % G: the
                       // patch embedding (conv bias, + pos, patch rows -> token rows; vit.py:21-29,42)
+  EPI_BDRS = 8        // EPI_BDR with a per-row factor between the dropout and the residual (vit_gemm_rowscale: drop
+                      // path).  A kind of its own, so that EPI_BDR's instantiations carry no trace of it
 };
 
 // Kinds whose row epilogue reads a second [m][n]-shaped bf16 operand (ReLU mask / residual).  Those reads are
@@ -530,7 +542,7 @@ enum EpiKind : int {
 // before it (one vmcnt counter).
 template <int KIND>
 VIT_DEV bool v4_has_pre(const EpiParams& e) {
-  return KIND == EPI_AUX || KIND == EPI_AUXM || (KIND == EPI_BDR && e.res != nullptr);
+  return KIND == EPI_AUX || KIND == EPI_AUXM || ((KIND == EPI_BDR || KIND == EPI_BDRS) && e.res != nullptr);
 }
 
 // One row piece of 4 columns of the LDS-image epilogue (v4_epilogue): the general epilogue, the split-K slab, or
@@ -783,13 +795,14 @@ VIT_DEV uint32_t pack_bf16x2(float a, float b) {
 
 // One row piece of 8 columns (v: fp32 accumulators in, the values as stored out when MK or CS need them).  Returns
 // the 8 mask bits (bit r = column j + r) when MK: dropout keep bits for EPI_BDR with dropout, else stored value > 0.
-// sh = 8 * (i % 4), the row's byte in a mask4 dword (EPI_AUXM).  The caller checks the row / column bounds.
+// sh = 8 * (i % 4), the row's byte in a mask4 dword (EPI_AUXM).  rs: the row's factor (EPI_BDRS; 0 = the row's branch
+// is dropped: the row stores its residual and its mask bits are clear).  The caller checks the row / column bounds.
 template <int KIND, int ACT, bool MK, bool CS>
 VIT_DEV uint32_t v4_epi_row8(const EpiParams& e, int64_t i, int64_t j, bf16_t* cp, const float (&b8)[8],
-                             float (&v)[8], uint4 pre, int sh) {
+                             float (&v)[8], uint4 pre, int sh, float rs = 1.f) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) v[r] *= e.alpha;
-  if (KIND == EPI_BIAS_ACT || KIND == EPI_BDR || KIND == EPI_PATCH) {
+  if (KIND == EPI_BIAS_ACT || KIND == EPI_BDR || KIND == EPI_BDRS || KIND == EPI_PATCH) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] += b8[r];
   }
@@ -821,7 +834,7 @@ VIT_DEV uint32_t v4_epi_row8(const EpiParams& e, int64_t i, int64_t j, bf16_t* c
     for (int r = 0; r < 8; ++r) v[r] = (bits >> r) & 1u ? v[r] : 0.f;
   }
   uint32_t keep = 0u;
-  if (KIND == EPI_BDR) {
+  if (KIND == EPI_BDR || KIND == EPI_BDRS) {
     if (e.use_drop) {
       const uint32_t base = (uint32_t)((i + e.row0) * e.drop_rs * e.n + j);
 #pragma unroll
@@ -830,6 +843,10 @@ VIT_DEV uint32_t v4_epi_row8(const EpiParams& e, int64_t i, int64_t j, bf16_t* c
         keep |= (uint32_t)k << r;
         v[r] = k ? v[r] * e.drop_scale : 0.f;
       }
+    }
+    if (KIND == EPI_BDRS) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) v[r] = rs != 0.f ? v[r] * rs : 0.f;
     }
     if (e.res) {
       float a[8];
@@ -850,7 +867,8 @@ VIT_DEV uint32_t v4_epi_row8(const EpiParams& e, int64_t i, int64_t j, bf16_t* c
     }
   }
   if (!MK) return 0u;
-  if (KIND == EPI_BDR && e.use_drop) return keep;
+  if (KIND == EPI_BDRS && rs == 0.f) return 0u;
+  if ((KIND == EPI_BDR || KIND == EPI_BDRS) && e.use_drop) return keep;
   uint32_t pos = 0u;
 #pragma unroll
   for (int r = 0; r < 8; ++r) pos |= (uint32_t)(v[r] > 0.f) << r;
@@ -884,7 +902,7 @@ VIT_DEV void v4_epilogue_d(const EpiParams& e, f32x4 (&acc)[2][2][4][2], float* 
   for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
     for (int r = 0; r < 8; ++r) b8[nh][r] = 0.f;
-  if ((KIND == EPI_BIAS_ACT || KIND == EPI_BDR || KIND == EPI_PATCH) && e.bias) {
+  if ((KIND == EPI_BIAS_ACT || KIND == EPI_BDR || KIND == EPI_BDRS || KIND == EPI_PATCH) && e.bias) {
 #pragma unroll
     for (int nh = 0; nh < 2; ++nh) {
       const int64_t j = j0 + nh * 128 + wc * 32 + cq;
@@ -910,6 +928,15 @@ VIT_DEV void v4_epilogue_d(const EpiParams& e, f32x4 (&acc)[2][2][4][2], float* 
 #pragma unroll
         for (int x = 0; x < 4; ++x) pre[nh][x] = v4_pre_load8<KIND>(e, rbase + 16 * x, j0 + nh * 128 + wc * 32 + cq);
     }
+    // EPI_BDRS: the 4 rows' factors, one load per row for both of its pieces, issued with the residual loads ahead of
+    // the half's stores (a load issued between them would wait for every store before it: one vmcnt counter).  4 B per
+    // row of a table the whole launch shares: L2-resident.
+    float rsc[4] = {1.f, 1.f, 1.f, 1.f};
+    if (KIND == EPI_BDRS) {
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if (rbase + 16 * x < e.m) rsc[x] = e.row_scale[(rbase + 16 * x + e.row0) * e.drop_rs];
+    }
 #pragma unroll
     for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
@@ -923,7 +950,8 @@ VIT_DEV void v4_epilogue_d(const EpiParams& e, f32x4 (&acc)[2][2][4][2], float* 
           // EPI_PATCH: output row (i / G) * Gs + i % G (32-bit: the host bounds m)
           const int64_t orow = KIND == EPI_PATCH ? (int64_t)((int)i / (int)e.grp) * e.grp_stride + (int)i % (int)e.grp : i;
           bits = v4_epi_row8<KIND, ACT, MK, CS>(e, i, j, (bf16_t*)e.c + orow * e.ldc + j, b8[nh], v,
-                                                has_pre ? pre[nh][x] : make_uint4(0u, 0u, 0u, 0u), 8 * (int)(i & 3));
+                                                has_pre ? pre[nh][x] : make_uint4(0u, 0u, 0u, 0u), 8 * (int)(i & 3),
+                                                rsc[x]);
           if (CS) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) cs[nh][r] += v[r];
@@ -1394,7 +1422,7 @@ int gemm_validate(const vit_gemm_desc* d) {
 
 // The epilogue's arguments from a descriptor; row0 = global row of local row 0 (dropout indices).  csum stays null:
 // the launcher sets it when the kernel fuses the column sums.
-EpiParams make_epi(const vit_gemm_desc* d, int64_t row0) {
+EpiParams make_epi(const vit_gemm_desc* d, int64_t row0, const float* row_scale) {
   EpiParams e{};
   e.c = d->c; e.ldc = d->ldc; e.m = d->m; e.n = d->n;
   e.alpha = d->alpha; e.beta = d->beta; e.bias = d->bias; e.act = d->act;
@@ -1409,6 +1437,7 @@ EpiParams make_epi(const vit_gemm_desc* d, int64_t row0) {
   e.row0 = row0;
   e.mask_out = (uint8_t*)d->mask_out;
   e.drop_rs = d->dropout_row_stride > 1 ? d->dropout_row_stride : 1;
+  e.row_scale = row_scale;
   e.vec = (d->n % 4 == 0) && (d->ldc % 4 == 0) && aligned(d->c, 16) && aligned(d->bias, 16) &&
           (!d->aux || d->aux_dtype == VIT_MASK4 || (d->ldaux % 4 == 0 && aligned(d->aux, 16))) &&
           (!d->res || (d->ldres % 4 == 0 && aligned(d->res, 16)));
@@ -1423,7 +1452,7 @@ EpiParams make_epi(const vit_gemm_desc* d, int64_t row0) {
 // cover (forward: both k-contiguous; ReLU backward: the input-gradient layout).  PLAIN is used on all three.
 constexpr bool kind_has(int kind, bool akc, bool bkc) {
   switch (kind) {
-    case EPI_BIAS_ACT: case EPI_BDR: case EPI_PATCH: return akc && bkc;
+    case EPI_BIAS_ACT: case EPI_BDR: case EPI_BDRS: case EPI_PATCH: return akc && bkc;
     case EPI_AUX: case EPI_AUXM: return akc && !bkc;
     default: return true;
   }
@@ -1439,7 +1468,9 @@ int v4_kind(const EpiParams& e, bool akc, bool bkc, bool out_bf, int split) {
   const bool lin = !e.aux && !e.use_drop && !e.res;            // nothing after bias / activation
   const bool no_ba = !e.bias && e.act == VIT_ACT_NONE;
   int kind = EPI_GENERAL;
-  if (rows_plain && lin && no_ba) kind = EPI_PLAIN;
+  if (e.row_scale) {                                           // the one fast kind that applies the row factor
+    if (rows_plain && !e.aux && e.act == VIT_ACT_NONE && (!e.res || e.res_dtype == VIT_BF16)) kind = EPI_BDRS;
+  } else if (rows_plain && lin && no_ba) kind = EPI_PLAIN;
   else if (rows_plain && lin && e.bias) kind = EPI_BIAS_ACT;
   else if (rows_plain && e.aux && no_ba && !e.use_drop && !e.res && e.aux_dtype != VIT_F32)
     kind = e.aux_dtype == VIT_BF16 ? EPI_AUX : EPI_AUXM;
@@ -1481,6 +1512,7 @@ void launch_bf16(int impl, int kind, bool to_bf, const Launch& L) {
       case EPI_PLAIN: return launch_v4<AKC, BKC, bf16_t, EPI_PLAIN>(L);
       case EPI_BIAS_ACT: return launch_v4<AKC, BKC, bf16_t, EPI_BIAS_ACT>(L);
       case EPI_BDR: return launch_v4<AKC, BKC, bf16_t, EPI_BDR>(L);
+      case EPI_BDRS: return launch_v4<AKC, BKC, bf16_t, EPI_BDRS>(L);
       case EPI_AUX: return launch_v4<AKC, BKC, bf16_t, EPI_AUX>(L);
       case EPI_AUXM: return launch_v4<AKC, BKC, bf16_t, EPI_AUXM>(L);
       case EPI_PATCH: return launch_v4<AKC, BKC, bf16_t, EPI_PATCH>(L);
@@ -1534,15 +1566,37 @@ extern "C" int vit_gemm_split_k_hint(int64_t m, int64_t n, int64_t k, int in_dty
 }
 
 
+// Which kernel one launch of a validated descriptor runs: impl = the kernel generation (0: the f32 kernel; 1 / 2 / 4:
+// gemm_impl's, demoted to 1 where the LDS-DMA kernels cannot take the operands), kind = v4_kind's (impl 4; else
+// EPI_GENERAL: those kernels have epilogue4 alone).  gemm_run launches exactly this, and vit_gemm_kernel_choice
+// reports it.
+struct Plan {
+  int impl, kind;
+  int64_t a_bytes, b_bytes;   // bf16 operand extents
+};
+static Plan gemm_plan(const vit_gemm_desc* d, const EpiParams& e) {
+  Plan p{0, EPI_GENERAL, 0, 0};
+  if (d->in_dtype != VIT_BF16) return p;
+  const bool akc = d->a_kcontig != 0, bkc = d->b_kcontig != 0;
+  // operand extents in bytes; v2/v4 (LDS-DMA) need whole 64-deep k-tiles (split boundaries are k-tile aligned) and
+  // operands < 2 GiB
+  p.a_bytes = (akc ? (d->m - 1) * d->lda + d->k : (d->k - 1) * d->lda + d->m) * 2;
+  p.b_bytes = (bkc ? (d->n - 1) * d->ldb + d->k : (d->k - 1) * d->ldb + d->n) * 2;
+  const bool dma_ok = d->k % BK == 0 && p.a_bytes < 0x7fffffffLL && p.b_bytes < 0x7fffffffLL;
+  p.impl = dma_ok ? gemm_impl(d->m, d->n) : 1;
+  if (p.impl == 4) p.kind = v4_kind(e, akc, bkc, d->out_dtype == VIT_BF16, d->split_k > 1 ? d->split_k : 1);
+  return p;
+}
+
 // One GEMM launch of a validated descriptor (+ the split-K reduce, + the column-sum pass when it is not fused);
 // row0 = global row of local row 0 (dropout indices).
-static int gemm_run(const vit_gemm_desc* d, int64_t row0, void* stream) {
+static int gemm_run(const vit_gemm_desc* d, int64_t row0, const float* row_scale, void* stream) {
   const int split = d->split_k > 1 ? d->split_k : 1;
   const bool in_bf = d->in_dtype == VIT_BF16, out_bf = d->out_dtype == VIT_BF16;
   const bool to_bf = out_bf && split == 1;              // the GEMM kernel stores C itself (else fp32 slabs / fp32 C)
   const bool akc = d->a_kcontig != 0, bkc = d->b_kcontig != 0;
   Launch L{};
-  L.e = make_epi(d, row0);
+  L.e = make_epi(d, row0, row_scale);
   L.s = VIT_STREAM(stream);
   GemmArgs& g = L.g;
   g.a = d->a; g.b = d->b; g.lda = d->lda; g.ldb = d->ldb; g.M = d->m; g.N = d->n; g.K = d->k;
@@ -1553,15 +1607,12 @@ static int gemm_run(const vit_gemm_desc* d, int64_t row0, void* stream) {
   }
 
   // plan: kernel generation, tile, epilogue kind, grid
-  int impl = 0, kind = EPI_GENERAL;                     // impl 0: the f32 kernel
+  const Plan plan = gemm_plan(d, L.e);
+  const int impl = plan.impl, kind = plan.kind;         // impl 0: the f32 kernel
   int64_t tile = FBM, bk = FBK;
   if (in_bf) {
-    // operand extents in bytes; v2/v4 (LDS-DMA) need whole 64-deep k-tiles (split boundaries are k-tile aligned) and
-    // operands < 2 GiB
-    L.a_bytes = (akc ? (d->m - 1) * d->lda + d->k : (d->k - 1) * d->lda + d->m) * 2;
-    L.b_bytes = (bkc ? (d->n - 1) * d->ldb + d->k : (d->k - 1) * d->ldb + d->n) * 2;
-    const bool dma_ok = d->k % BK == 0 && L.a_bytes < 0x7fffffffLL && L.b_bytes < 0x7fffffffLL;
-    impl = dma_ok ? gemm_impl(d->m, d->n) : 1;
+    L.a_bytes = plan.a_bytes;
+    L.b_bytes = plan.b_bytes;
     tile = impl == 4 ? 256 : BM;
     bk = BK;
     g.nitems = ((d->m + 255) / 256) * ((d->n + 255) / 256) * split;   // v4: tiles x K-slices, split-major
@@ -1574,7 +1625,6 @@ static int gemm_run(const vit_gemm_desc* d, int64_t row0, void* stream) {
   L.grid = dim3((unsigned)(g.tiles_m * g.tiles_n), (unsigned)split);
   bool cs_fused = false;
   if (impl == 4) {
-    kind = v4_kind(L.e, akc, bkc, out_bf, split);
     const bool wide = kind != EPI_SLAB && kind != EPI_GENERAL;   // bf16 rows straight from the accumulators
     cs_fused = wide && d->colsum_part;
     if (cs_fused) L.e.csum = d->colsum_part;
@@ -1618,15 +1668,16 @@ static int gemm_run(const vit_gemm_desc* d, int64_t row0, void* stream) {
 // one launch and the remaining tile rows run split-K over the otherwise idle CUs: fp32 slabs in the caller's
 // workspace, then the deterministic reduce applies the same epilogue (dropout indices keep the global row; column
 // sums land in the same colsum_part rows).  Without a large enough workspace the GEMM runs unsplit.
-extern "C" int vit_gemm(const vit_gemm_desc* d, void* stream) {
+static int gemm_entry(const vit_gemm_desc* d, const float* row_scale, void* stream) {
   if (const int rc = gemm_validate(d)) return rc;
+  VIT_REQUIRE(aligned(row_scale, 4), "vit_gemm_rowscale: row_scale must be 4-B aligned");
   int64_t m_main = 0;
   const int sk = tail_split(d, &m_main);
   if (sk <= 1 || !d->workspace || d->workspace_bytes < vit_gemm_workspace_bytes(d))
-    return gemm_run(d, d->dropout_row0, stream);
+    return gemm_run(d, d->dropout_row0, row_scale, stream);
   vit_gemm_desc dm = *d;
   dm.m = m_main;
-  if (const int rc = gemm_run(&dm, d->dropout_row0, stream)) return rc;
+  if (const int rc = gemm_run(&dm, d->dropout_row0, row_scale, stream)) return rc;
   auto esz = [](int32_t t) { return t == VIT_BF16 ? (int64_t)2 : (int64_t)4; };
   const int64_t r = m_main;
   vit_gemm_desc dt = *d;
@@ -1639,5 +1690,31 @@ extern "C" int vit_gemm(const vit_gemm_desc* d, void* stream) {
   if (d->colsum_part) dt.colsum_part = d->colsum_part + (r / 256) * d->n;
   dt.m = d->m - r;
   dt.split_k = sk;
-  return gemm_run(&dt, d->dropout_row0 + r, stream);
+  return gemm_run(&dt, d->dropout_row0 + r, row_scale, stream);
+}
+
+extern "C" int vit_gemm(const vit_gemm_desc* d, void* stream) { return gemm_entry(d, nullptr, stream); }
+
+static_assert(EPI_BDR == VIT_EPI_BDR && EPI_BDRS == VIT_EPI_BDRS && EPI_GENERAL == VIT_EPI_GENERAL &&
+              EPI_SLAB == VIT_EPI_SLAB, "vit_hip.h names the epilogue kinds vit_gemm_kernel_choice reports");
+
+// The kernel and epilogue kind vit_gemm / vit_gemm_rowscale would launch for this descriptor under the current options
+// (the whole-round launch where a split-K tail follows): gemm_run's own plan, no launch.
+extern "C" int vit_gemm_kernel_choice(const vit_gemm_desc* d, const float* row_scale, int32_t* impl, int32_t* kind) {
+  if (const int rc = gemm_validate(d)) return rc;
+  VIT_REQUIRE(impl && kind, "vit_gemm_kernel_choice: null output pointer");
+  int64_t m_main = 0;
+  vit_gemm_desc dm = *d;
+  if (tail_split(d, &m_main) > 1 && d->workspace && d->workspace_bytes >= vit_gemm_workspace_bytes(d)) dm.m = m_main;
+  const Plan p = gemm_plan(&dm, make_epi(&dm, d->dropout_row0, row_scale));
+  *impl = p.impl;
+  *kind = p.kind;
+  return VIT_OK;
+}
+
+// vit_gemm with a per-row factor between the dropout and the residual add (vit_hip.h): row_scale is indexed by the
+// dropout's row index, so a row range (dropout_row0, the split-K tail) or a row-strided view (dropout_row_stride)
+// addresses the whole tensor's table.  NULL is vit_gemm itself.
+extern "C" int vit_gemm_rowscale(const vit_gemm_desc* d, const float* row_scale, void* stream) {
+  return gemm_entry(d, row_scale, stream);
 }

@@ -289,6 +289,24 @@ __global__ __launch_bounds__(256) void mask4_apply_kernel(const TI* __restrict__
   }
 }
 
+// Drop path: the per-row factor table of vit_drop_path_rows.  blockIdx.y = l * 2 + site, so the layer's threshold and
+// scale are uniform reads of the kernel arguments; one draw per image, written to its T token rows.
+struct DropPathTab {
+  uint32_t thr[VIT_DROP_PATH_MAX_LAYERS];
+  float scale[VIT_DROP_PATH_MAX_LAYERS];
+};
+__global__ __launch_bounds__(256) void drop_path_rows_kernel(float* __restrict__ out, uint32_t seed, uint32_t L,
+                                                             uint32_t BT, uint32_t T, DropPathTab tab) {
+  const uint32_t ls = blockIdx.y, l = ls >> 1;
+  // site_seed(seed, L + l, site) of the host package: the element-dropout streams use layers 0 .. L-1
+  const uint32_t sseed = vit_hash_u32(seed * 0x632BE5ABu + 0x1234567u, (L + l) * 2u + (ls & 1u));
+  const uint32_t thr = tab.thr[l];
+  const float scale = tab.scale[l];
+  float* o = out + (int64_t)ls * BT;
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < BT; t += gridDim.x * blockDim.x)
+    o[t] = vit_hash_u32(sseed, t / T) >= thr ? scale : 0.f;
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y,
                                                        T* __restrict__ dx, int64_t n) {
@@ -760,6 +778,26 @@ extern "C" int vit_mask4_apply(const void* x, int64_t ldx, int32_t x_dtype, void
   else MA(float, float);
 #undef MA
   return vit::check_launch("vit_mask4_apply");
+}
+
+extern "C" int vit_drop_path_rows(float* out, uint32_t seed, int64_t L, int64_t B, int64_t T, const float* rates,
+                                  void* stream) {
+  VIT_REQUIRE(out && rates, "vit_drop_path_rows: null pointer");
+  VIT_REQUIRE(L > 0 && B > 0 && T > 0, "vit_drop_path_rows: bad sizes L=%lld B=%lld T=%lld", (long long)L, (long long)B,
+              (long long)T);
+  VIT_REQUIRE(L <= VIT_DROP_PATH_MAX_LAYERS, "vit_drop_path_rows: L=%lld exceeds VIT_DROP_PATH_MAX_LAYERS=%d",
+              (long long)L, VIT_DROP_PATH_MAX_LAYERS);
+  VIT_REQUIRE(B < (1LL << 31) && T < (1LL << 31) && B * T < (1LL << 31), "vit_drop_path_rows: B * T must be below 2^31");
+  DropPathTab tab{};
+  for (int64_t l = 0; l < L; ++l) {
+    const float p = rates[l];
+    VIT_REQUIRE(p >= 0.f && p < 1.f, "vit_drop_path_rows: rate %g of layer %lld outside [0, 1)", (double)p, (long long)l);
+    tab.thr[l] = vit_drop_threshold(p);
+    tab.scale[l] = 1.0f / (1.0f - p);
+  }
+  const dim3 grid(grid_for(B * T, 256, 1024), (unsigned)(2 * L));
+  drop_path_rows_kernel<<<grid, 256, 0, VIT_STREAM(stream)>>>(out, seed, (uint32_t)L, (uint32_t)(B * T), (uint32_t)T, tab);
+  return vit::check_launch("vit_drop_path_rows");
 }
 
 extern "C" int vit_relu_bwd(const void* dy, const void* y, void* dx, int32_t dtype, int64_t n, void* stream) {

@@ -375,6 +375,9 @@ def main():
     ap.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
                     help="keep an exponential moving average of the weights with this decay inside the optimizer "
                          "step, validate on it and save it as ema_state_dict (default: none, as the reference)")
+    ap.add_argument("--drop-path", type=float, default=0.0, metavar="RATE",
+                    help="stochastic depth: drop each residual branch per image, block l of L at rate RATE * l / (L - 1) "
+                         "(timm's linear rule; DeiT-B trains with 0.1; default 0: off, as the reference)")
     ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="F",
                     help="label smoothing of the training loss (default 0: the reference's plain cross entropy)")
     ap.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
@@ -434,7 +437,7 @@ def main():
     D, H, L = config.PRESETS[args.model]
     cfg = config.ViTConfig(input_channels=3, num_classes=args.classes, num_patches=n_patches, embedding_size=D,
                            patch_size=args.patch, num_heads=H, num_blocks=L, precision=dtype,
-                           batch_size=args.batch, device="cpu")
+                           batch_size=args.batch, device="cpu", drop_path_rate=args.drop_path)
     mix = None
     if args.mixup > 0 or args.cutmix > 0:
         from VisionTransformer.data import BatchMix
