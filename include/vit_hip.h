@@ -482,6 +482,44 @@ int vit_adamw_ema(const vit_tensor_chunk* table_dev, float* const* ema_dev, int6
 int vit_ema_swap(const vit_tensor_chunk* table_dev, float* const* ema_dev, int64_t nchunks, int32_t shadow_dtype,
                  void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * LAMB: layer-wise trust ratios over the same chunk tables (purely added entry points, ABI 18).  The reference has no
+ * counterpart (train.py:66 is AdamW); the formulas are those of timm's Lamb / NVIDIA's FusedLAMB with bias
+ * correction, decoupled weight decay added into the update, for a tensor w at step t:
+ *   g = grad * gs * coef                          (gs = grad_scale; coef = clip[1] with clip, else 1)
+ *   m = b1*m + (1-b1)*g;   v = b2*v + (1-b2)*g^2
+ *   u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd * w
+ *   r = |w|_2 / |u|_2 over the whole tensor where `adapt` is set and both norms are > 0, else 1;  min(r, 1) with
+ *       `trust_clip`
+ *   w -= lr * r * u;   shadow = (dtype) w;   e += ema_weight * (w - e) where the chunk keeps an EMA
+ * r needs the whole tensor before any element of it moves, so a step is three launches on one stream, no host sync,
+ * no atomics, every sum fp64 in a fixed order (bitwise reproducible):
+ *   vit_lamb_moments: one workgroup per chunk.  Writes m and v; forms u in fp32 and writes partial[2i] = sum w^2 and
+ *                     partial[2i+1] = sum u^2 over chunk i (each fp32 value squared and summed in fp64).  w is read only.
+ *   vit_lamb_trust:   one workgroup per tensor.  tensor_first[ntensors + 1] (device, int32) holds the index of each
+ *                     tensor's first chunk and nchunks as its last entry: a tensor's chunks are consecutive in the
+ *                     table.  Writes trust[tensor] (fp32) by the rule above from the fp64 sums of its chunks' partials;
+ *                     any number of chunks per tensor.
+ *   vit_lamb_update:  one workgroup per chunk.  Forms u again from the m and v the first pass wrote (u is never stored:
+ *                     about 42 B per element over both passes against vit_adamw's 30) with the same arithmetic, so the
+ *                     u that moves w is bit for bit the u whose norm was taken, and applies the last line with
+ *                     r = trust[tensor_of_chunk[i]] (device, int32 [nchunks]).  ema_dev as in vit_adamw_ema; NULL
+ *                     means no EMA at all, and then ema_weight is not read.
+ * bias_corr1 = 1 - b1^t and bias_corr2 = 1 - b2^t must lie in (0, 1], eps must not be negative, and the second pass
+ * takes the same eps, weight_decay and bias corrections as the first.  clip is NULL or vit_grad_clip_finish's block:
+ * when clip[2] != 0 (skipped step) all three return at once, so neither w, m, v, the shadows, the EMA, the partials nor
+ * trust[] change.  The AdamW entry points above are untouched.
+ * ------------------------------------------------------------------------------------------------------------ */
+int vit_lamb_moments(const vit_tensor_chunk* table_dev, int64_t nchunks, float beta1, float beta2, float eps,
+                     float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, const float* clip,
+                     double* partial /* [2 * nchunks] */, void* stream);
+int vit_lamb_trust(const double* partial /* [2 * nchunks] */, const int32_t* tensor_first /* [ntensors + 1] */,
+                   int64_t ntensors, int32_t adapt, int32_t trust_clip, float* trust /* [ntensors] */,
+                   const float* clip, void* stream);
+int vit_lamb_update(const vit_tensor_chunk* table_dev, float* const* ema_dev, const int32_t* tensor_of_chunk,
+                    const float* trust, int64_t nchunks, float lr, float eps, float weight_decay, float bias_corr1,
+                    float bias_corr2, int32_t shadow_dtype, float ema_weight, const float* clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

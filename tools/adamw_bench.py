@@ -8,7 +8,9 @@ AdamW kernel alone with their achieved TB/s (4 B and 30 B per element).
 
 --ema times, the same way, FusedAdamW plain, FusedAdamW(ema_decay=0.9999) (the EMA inside the one launch) and the plain
 step followed by torch._foreach_lerp_ over separate EMA tensors (what AveragedModel.update_parameters runs); plus the
-EMA kernel and the AdamW kernel alone with their achieved TB/s (38 B and 30 B per element)."""
+EMA kernel and the AdamW kernel alone with their achieved TB/s (38 B and 30 B per element).
+
+--lamb times FusedAdamW against FusedLamb the same way (lamb_bench)."""
 import argparse
 import os
 import sys
@@ -190,9 +192,92 @@ def ema_bench(reps, warmup=3, decay=0.9999):
     print(f"  adamw_ema / adamw: {_stats(kt['adamw_ema'])[0] / _stats(kt['adamw'])[0]:.3f} (38 / 30 = {38 / 30:.3f})")
 
 
+def lamb_bench(reps, warmup=3):
+    """FusedAdamW against FusedLamb (three launches per table) on the C2 parameter set, interleaved rep by rep, one
+    group and timm's two weight-decay groups; then the AdamW kernel and LAMB's three launches in sequence with an event
+    between each, with their achieved TB/s (30 B per element; 24 for the first pass, 0 for the finish, 18 for the
+    second pass: 42 over both)."""
+    from VisionTransformer import _ops, config, vit
+    from VisionTransformer.optim import FusedAdamW, FusedLamb, param_groups_weight_decay
+    dev = torch.device("cuda", 0)
+    cfg = config.ViTConfig.preset("base", img_size=224, batch_size=256, num_classes=1000, device="cpu")
+    torch.manual_seed(0)
+
+    def model():
+        # the gradients as the engine hands them over: views of one flat buffer
+        m = vit.VisionTransformer(cfg).to(dev)
+        flat = torch.randn(sum(p.numel() for p in m.parameters()), device=dev)
+        off = 0
+        for p in m.parameters():
+            p.grad = flat[off:off + p.numel()].view(p.shape)
+            off += p.numel()
+        return m
+
+    arms = {}
+    for name, cls, split in (("adamw", FusedAdamW, False), ("lamb", FusedLamb, False),
+                             ("adamw_2_groups", FusedAdamW, True), ("lamb_2_groups", FusedLamb, True)):
+        m = model()
+        arms[name] = (m, cls(param_groups_weight_decay(m, 0.05) if split else m.parameters(), lr=1e-3,
+                             weight_decay=0.05))
+    n = sum(p.numel() for p in arms["adamw"][0].parameters())
+    times = {k: [] for k in arms}
+    for i in range(reps + warmup):
+        for name, (_, opt) in arms.items():      # interleaved: box drift hits every arm alike
+            t = _timed(opt.step)
+            if i >= warmup:
+                times[name].append(t)
+    print(f"C2 parameter set: {len(list(arms['adamw'][0].parameters()))} tensors, {n / 1e6:.1f}M elements; {reps} reps "
+          f"after {warmup} warm-up, device events around the whole step (host launches included), us: median "
+          "[min .. max]")
+    for name, ts in times.items():
+        print("  %-22s %8.1f [%8.1f .. %8.1f]" % ((name,) + _stats(ts)))
+    med = {k: _stats(v)[0] for k, v in times.items()}
+    print(f"  lamb / adamw: {med['lamb'] / med['adamw']:.3f} one group, "
+          f"{med['lamb_2_groups'] / med['adamw_2_groups']:.3f} two groups (bytes: 42 / 30 = {42 / 30:.3f})")
+    # the kernels on one table: the AdamW update, then LAMB's three launches in sequence with an event between each
+    ps = [p.detach() for p in arms["adamw"][0].parameters()]
+    gs = [p.grad for p in arms["adamw"][0].parameters()]
+    ms, vs = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+    sh = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) for p in ps]
+    entries = list(zip(ps, gs, ms, vs, sh))
+    tab, nc = _ops.build_chunk_table(entries, dev)
+    first, owner, nt, _ = _ops.build_tensor_index(entries, dev)
+    partial = torch.empty(2 * nc, dtype=torch.float64, device=dev)
+    trust = torch.ones(nt, device=dev)
+    adam = (1e-3, 0.9, 0.999, 1e-8, 0.05, 0.1, 0.001, 1.0, torch.bfloat16)
+    seq = [("lamb_moments", 24, lambda: _ops.lamb_moments(tab, nc, 0.9, 0.999, 1e-6, 0.05, 0.1, 0.001, 1.0, partial)),
+           ("lamb_trust", 0, lambda: _ops.lamb_trust(partial, first, nt, trust)),
+           ("lamb_update", 18, lambda: _ops.lamb_update(tab, owner, trust, nc, 1e-3, 1e-6, 0.05, 0.1, 0.001,
+                                                        torch.bfloat16))]
+    kt = {k: [] for k in ["adamw"] + [k for k, _, _ in seq] + ["lamb sequence"]}
+    for i in range(reps + warmup):
+        t = _timed(lambda: _ops.adamw(tab, nc, *adam))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(seq) + 1)]
+        ev[0].record()
+        for j, (_, _, fn) in enumerate(seq):
+            fn()
+            ev[j + 1].record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            kt["adamw"].append(t)
+            for j, (k, _, _) in enumerate(seq):
+                kt[k].append(ev[j].elapsed_time(ev[j + 1]) * 1e3)
+            kt["lamb sequence"].append(ev[0].elapsed_time(ev[-1]) * 1e3)
+    print(f"kernels ({nc} workgroups, {nt} tensors; event to event, so each figure includes a launch gap), us: median "
+          "[min .. max], achieved TB/s at the median")
+    bpe = dict([("adamw", 30), ("lamb sequence", 42)] + [(k, b) for k, b, _ in seq])
+    for k, ts in kt.items():
+        m_, lo, hi = _stats(ts)
+        bw = f"{n * bpe[k] / m_ / 1e6:5.2f} TB/s ({bpe[k]} B / element)" if bpe[k] else f"{nt} workgroups"
+        print("  %-22s %8.1f [%8.1f .. %8.1f]  %s" % (k, m_, lo, hi, bw))
+    ratio = _stats(kt["lamb sequence"])[0] / _stats(kt["adamw"])[0]
+    print(f"  lamb sequence / adamw: {ratio:.3f} (42 / 30 = {42 / 30:.3f}; 1.25 x that = {1.25 * 42 / 30:.3f})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--lamb", action="store_true", help="time FusedAdamW against FusedLamb and LAMB's three launches")
     ap.add_argument("--clip", action="store_true", help="time the unclipped, fused-clipped and clip_grad_norm_ steps")
     ap.add_argument("--ema", action="store_true", help="time the plain, fused-EMA and step + _foreach_lerp_ steps")
     args = ap.parse_args()
@@ -200,6 +285,8 @@ def main():
         return clip_bench(args.reps)
     if args.ema:
         return ema_bench(args.reps)
+    if args.lamb:
+        return lamb_bench(args.reps)
     from VisionTransformer import _ops, config, vit
     dev = torch.device("cuda", 0)
     cfg = config.ViTConfig.preset("base", img_size=224, batch_size=256, num_classes=1000, device="cpu")

@@ -118,6 +118,9 @@ _SIGS = {
     "vit_gemm_rowscale": (ctypes.c_int, [ctypes.POINTER(GemmDesc), _P, _P]),
     "vit_gemm_kernel_choice": (ctypes.c_int, [ctypes.POINTER(GemmDesc), _P, ctypes.POINTER(_I32),
                                               ctypes.POINTER(_I32)]),
+    "vit_lamb_moments": (ctypes.c_int, [_P, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "vit_lamb_trust": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P]),
+    "vit_lamb_update": (ctypes.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I32, _F, _P, _P]),
 }
 
 EPI_BDR, EPI_SLAB, EPI_GENERAL, EPI_BDRS = 3, 4, 5, 8    # VIT_EPI_* (vit_hip.h): kinds vit_gemm_kernel_choice reports

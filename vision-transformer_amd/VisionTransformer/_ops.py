@@ -651,3 +651,74 @@ def ema_swap(table_dev, ema_dev, nchunks, shadow_dtype, stream=None):
     """vit_ema_swap: p <-> e for every chunk whose EMA pointer is set, and shadow = (dtype) p there."""
     _check_ema(ema_dev, nchunks)
     _lib.call("vit_ema_swap", _ptr(table_dev), _ptr(ema_dev), nchunks, dtype_code(shadow_dtype), _stream(stream))
+
+
+# ---- LAMB (vit_hip.h "LAMB") ----------------------------------------------------------------------------------------
+def build_tensor_index(entries, device):
+    """The per-tensor maps that go with build_chunk_table(entries), cut by the same _chunks(): `tensor_first`
+    (int32 [ntensors + 1], the index of each tensor's first chunk, nchunks last) and `tensor_of_chunk` (int32
+    [nchunks]).  `entries` is any list whose items start with the parameter.  Returns (tensor_first, tensor_of_chunk,
+    ntensors, nchunks), the first two on `device`."""
+    first, owner = [0], []
+    for i, ent in enumerate(entries):
+        n = len(_chunks(ent[0].numel()))
+        if n == 0:
+            raise ValueError("a tensor without elements has no chunk, so it cannot have a trust ratio")
+        owner.extend([i] * n)
+        first.append(first[-1] + n)
+    return (torch.tensor(first, dtype=torch.int32).to(device), torch.tensor(owner, dtype=torch.int32).to(device),
+            len(entries), len(owner))
+
+
+def _check_lamb_buffer(t, dtype, numel, what):
+    _need_cuda(t)
+    if t is None or t.dtype != dtype or t.numel() < numel or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} device tensor of at least {numel} elements")
+
+
+def lamb_moments(table_dev, nchunks, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale, partial,
+                 stream=None, clip=None):
+    """vit_lamb_moments: m and v of every chunk, and partial[2i], partial[2i + 1] = the chunk's fp64 sums of p^2 and
+    u^2.  `partial`: float64 device tensor of at least 2 * nchunks elements.  `clip` as in adamw()."""
+    _need_cuda(table_dev)
+    _check_lamb_buffer(partial, torch.float64, 2 * nchunks, "partial")
+    if clip is not None:
+        _check_clip(clip)
+    _lib.call("vit_lamb_moments", _ptr(table_dev), nchunks, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2,
+              grad_scale, _ptr(clip), _ptr(partial), _stream(stream))
+
+
+def lamb_trust(partial, tensor_first, ntensors, trust, adapt=True, trust_clip=False, stream=None, clip=None):
+    """vit_lamb_trust: trust[i] = |p| / |u| of tensor i from lamb_moments' partials where `adapt` is set and both norms
+    are positive, else 1; at most 1 with `trust_clip`.  `tensor_first` from build_tensor_index."""
+    _check_lamb_buffer(tensor_first, torch.int32, ntensors + 1, "tensor_first")
+    if tensor_first.numel() != ntensors + 1:
+        raise ValueError(f"tensor_first must have ntensors + 1 = {ntensors + 1} elements")
+    _check_lamb_buffer(trust, torch.float32, ntensors, "trust")
+    if partial is None or partial.dtype != torch.float64 or not partial.is_contiguous():
+        raise ValueError("partial must be a contiguous float64 device tensor")
+    _need_cuda(partial)
+    if clip is not None:
+        _check_clip(clip)
+    _lib.call("vit_lamb_trust", _ptr(partial), _ptr(tensor_first), ntensors, int(bool(adapt)), int(bool(trust_clip)),
+              _ptr(trust), _ptr(clip), _stream(stream))
+
+
+def lamb_update(table_dev, tensor_of_chunk, trust, nchunks, lr, eps, weight_decay, bias_corr1, bias_corr2,
+                shadow_dtype, ema_dev=None, ema_decay=None, stream=None, clip=None):
+    """vit_lamb_update: p -= lr * trust[tensor of the chunk] * u, the shadows, and with `ema_dev` / `ema_decay` the
+    EMA of adamw_ema() for every chunk whose pointer is set.  eps, weight_decay and the bias corrections are those
+    lamb_moments was given."""
+    _need_cuda(table_dev)
+    _check_lamb_buffer(tensor_of_chunk, torch.int32, nchunks, "tensor_of_chunk")
+    if tensor_of_chunk.numel() != nchunks:
+        raise ValueError(f"tensor_of_chunk must have nchunks = {nchunks} elements")
+    _check_lamb_buffer(trust, torch.float32, 1, "trust")
+    ema_w = 0.0
+    if ema_dev is not None:
+        _check_ema(ema_dev, nchunks)
+        ema_w = 1.0 - float(ema_decay)
+    if clip is not None:
+        _check_clip(clip)
+    _lib.call("vit_lamb_update", _ptr(table_dev), _ptr(ema_dev), _ptr(tensor_of_chunk), _ptr(trust), nchunks, lr, eps,
+              weight_decay, bias_corr1, bias_corr2, dtype_code(shadow_dtype), ema_w, _ptr(clip), _stream(stream))

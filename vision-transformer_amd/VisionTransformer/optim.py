@@ -12,6 +12,7 @@ and / or MixedLabels (mixup / CutMix) the same against a smoothed two-label targ
 import collections
 import contextlib
 import math
+import struct
 import typing
 
 import torch
@@ -69,10 +70,11 @@ def _closure_loss(closure):
 class _StepTable:
     """One cached launch of the fused step: the device chunk table over the parameters `params` (and, where any of
     them has an EMA, the EMA pointer array cut alike), with what valid() compares to tell that it still describes
-    them.  `keep` holds every tensor whose pointer the device table carries."""
+    them.  `keep` holds every tensor whose pointer the device table carries.  `lamb` is FusedLamb's: the tensor index
+    of the table and the buffers its three launches pass along (_LambIndex), made at the table's first LAMB step."""
 
     __slots__ = ("version", "params", "grads", "grad_ptrs", "param_ptrs", "moments", "emas", "dev_tab", "ema_dev",
-                 "nchunks", "shadow_dtype", "device", "keep")
+                 "nchunks", "shadow_dtype", "device", "keep", "lamb")
 
     @classmethod
     def build(cls, opt, ps):
@@ -94,7 +96,18 @@ class _StepTable:
         else:
             tab.ema_dev, _ = _ops.build_ema_pointers(list(zip(ps, tab.emas)), tab.device)
         tab.param_ptrs, tab.grad_ptrs = [p.data_ptr() for p in ps], [g.data_ptr() for g in tab.grads]
+        tab.lamb = None
         return tab
+
+    def lamb_index(self):
+        if self.lamb is None:
+            first, owner, ntensors, nchunks = _ops.build_tensor_index(self.keep, self.device)
+            if nchunks != self.nchunks:
+                raise RuntimeError("FusedLamb: the tensor index disagrees with the chunk table")
+            self.lamb = _LambIndex(first, owner, ntensors,
+                                   torch.zeros(2 * nchunks, dtype=torch.float64, device=self.device),
+                                   torch.ones(ntensors, dtype=torch.float32, device=self.device), _ops.CHUNK)
+        return self.lamb
 
     def valid(self, opt, ps):
         """Same optimizer version, same parameters, every parameter still holds the same .grad tensor object and the
@@ -122,6 +135,10 @@ class _StepTable:
         return True
 
 
+# tensor_first int32 [ntensors + 1], tensor_of_chunk int32 [nchunks], the fp64 [2 * nchunks] norm partials, the fp32
+# [ntensors] trust ratios (ones until a step writes them): all on the table's device, sized once; `chunk` is the
+# _ops.CHUNK they were cut with
+_LambIndex = collections.namedtuple("_LambIndex", "tensor_first tensor_of_chunk ntensors partial trust chunk")
 _SwapKey = collections.namedtuple("_SwapKey", "param ptr ema shadow")      # what a parameter's swap entry was cut from
 _SwapTable = collections.namedtuple("_SwapTable", "dev_tab ema_dev nchunks shadow_dtype keep")
 
@@ -386,6 +403,104 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
         self._ema_swapped = not self._ema_swapped
 
 
+_LAMB_GROUP_KEYS = ("always_adapt", "trust_clip")
+
+
+def _as_f32(x):
+    """The value a Python float takes as a `float` argument of the library."""
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def _check_lamb_flags(group):
+    for k in _LAMB_GROUP_KEYS:
+        if not isinstance(group[k], bool):
+            raise ValueError(f"{k} must be a bool (got {group[k]!r})")
+
+
+class FusedLamb(FusedAdamW):
+    """LAMB (timm's Lamb / NVIDIA's FusedLAMB, bias correction on; the reference has none) over FusedAdamW's tables,
+    counters, clipping, EMA and swap: only the per-table launch differs.  For a tensor w of a group at step count t
+
+        g = grad * grad_scale * coef          m = b1 m + (1 - b1) g          v = b2 v + (1 - b2) g^2
+        u = (m / (1 - b1^t)) / (sqrt(v) / sqrt(1 - b2^t) + eps) + weight_decay * w
+        r = |w| / |u| where both norms are positive, else 1      (r = 1 if weight_decay == 0 and not always_adapt)
+        r = min(r, 1) with trust_clip                             w -= lr * r * u
+
+    in three launches per table (include/vit_hip.h "LAMB"): the moments and per-chunk fp64 norm partials, one workgroup
+    per tensor turning them into a ratio, and the update, which forms u again instead of reading it back.  Every group
+    goes through them, a `weight_decay == 0` group too: its ratios are written as 1 by the second launch, so there is
+    one set of kernels and one set of bits to test.  `always_adapt` and `trust_clip` are `param_groups`
+    keys, per group and serialised with it; the state keys are FusedAdamW's, so checkpoints interchange with it and
+    with torch.optim.AdamW (a loaded group that lacks the two keys keeps this optimizer's current values).  On a step
+    skipped for a non-finite norm none of the three launches writes anything.  `trust_ratios()` reads the last step's
+    ratios without a sync."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, always_adapt=False,
+                 trust_clip=False, grad_scale=1.0, max_grad_norm=None, skip_nonfinite=True, ema_decay=None):
+        flags = dict(always_adapt=always_adapt, trust_clip=trust_clip)
+        _check_lamb_flags(flags)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+        self.defaults.update(flags)
+        for group in self.param_groups:
+            for k, v in flags.items():
+                group.setdefault(k, v)
+        self._stepped = []        # the tables of the last step, for trust_ratios()
+
+    def load_state_dict(self, state_dict):
+        mine = [{k: g[k] for k in _LAMB_GROUP_KEYS} for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, kept in zip(self.param_groups, mine):      # a torch AdamW / FusedAdamW checkpoint has neither key
+            for k, v in kept.items():
+                group.setdefault(k, v)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        self._stepped = []        # (not in invalidate(): a later group's fresh state invalidates in mid-step)
+        return super().step(closure)
+
+    def _table(self, key, ps):
+        """FusedAdamW's, and a table rebuilt over the very same parameters (new gradient tensors, a new EMA) inherits
+        the tensor index and buffers of the one it replaces: same tensors, same cut, and the ratios of the last step
+        stay readable through a skipped one."""
+        old = self._tables.get(key)
+        tab = super()._table(key, ps)
+        if (tab is not old and old is not None and old.lamb is not None and old.lamb.chunk == _ops.CHUNK
+                and tab.device == old.device and len(old.params) == len(ps)
+                and all(a is b for a, b in zip(old.params, ps))):
+            tab.lamb = old.lamb
+        return tab
+
+    def _adamw(self, tab, group, t, clip=None):
+        """The LAMB update of one table's parameters, all at step count `t`."""
+        _check_lamb_flags(group)
+        # The betas as the kernels receive them, rounded to fp32: the recurrence runs with 1 - fl32(b2), which is
+        # 1.3e-5 (relative) away from 1 - 0.999, so bias corrections formed from the unrounded betas would leave
+        # sqrt(v_hat), u and with it every ratio off by 6e-6 in the first steps.  From the rounded ones the step is
+        # exactly LAMB with betas 1e-8 away from the group's.
+        b1, b2 = (_as_f32(b) for b in group["betas"])
+        eps, wd, bc1, bc2 = group["eps"], group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t
+        ix = tab.lamb_index()
+        ema = self.ema_decay is not None
+        _ops.lamb_moments(tab.dev_tab, tab.nchunks, b1, b2, eps, wd, bc1, bc2, self.grad_scale, ix.partial, clip=clip)
+        _ops.lamb_trust(ix.partial, ix.tensor_first, ix.ntensors, ix.trust,
+                        adapt=wd != 0 or group["always_adapt"], trust_clip=group["trust_clip"], clip=clip)
+        _ops.lamb_update(tab.dev_tab, ix.tensor_of_chunk, ix.trust, tab.nchunks, group["lr"], eps, wd, bc1, bc2,
+                         tab.shadow_dtype, ema_dev=tab.ema_dev if ema else None,
+                         ema_decay=self.ema_decay if ema else None, clip=clip)
+        self._stepped.append(tab)
+
+    def trust_ratios(self):
+        """{parameter: its trust ratio r in the last step}, for every parameter that step updated: fresh 0-d device
+        tensors (views of one copy per table, made on the current stream), so a caller can keep them and read them
+        later without a sync in between, as with grad_norm().  1 where the rule says 1."""
+        out = {}
+        for tab in self._stepped:
+            r = tab.lamb.trust.clone()
+            out.update((p, r[i]) for i, p in enumerate(tab.params))
+        return out
+
+
 class _XentFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels):
@@ -564,12 +679,117 @@ class EmaAdamW(_EmaSurface, _HostClip, torch.optim.AdamW):
         self._ema_swapped = not self._ema_swapped
 
 
+class Lamb(_EmaSurface, _HostClip, torch.optim.Optimizer):
+    """The host path's counterpart of FusedLamb, in torch ops on whatever device and dtype the parameters have: the
+    same formulas (FusedLamb's docstring), defaults, `param_groups` keys and state keys, `max_grad_norm` /
+    `skip_nonfinite` as ClippedAdamW has them, `ema_decay` and the swap surface as EmaAdamW, and trust_ratios().  As
+    on the host path's AdamW classes a skipped step does not advance the `step` counters."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, always_adapt=False,
+                 trust_clip=False, max_grad_norm=None, skip_nonfinite=True, ema_decay=None):
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("invalid LAMB hyper-parameters")
+        flags = dict(always_adapt=always_adapt, trust_clip=trust_clip)
+        _check_lamb_flags(flags)
+        _check_max_grad_norm(max_grad_norm)
+        _check_ema_decay(ema_decay)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **flags))
+        self.ema_decay = ema_decay
+        self._init_clip(max_grad_norm, skip_nonfinite)
+        self._ratios = {}
+
+    def load_state_dict(self, state_dict):
+        mine = [{k: g[k] for k in _LAMB_GROUP_KEYS} for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, kept in zip(self.param_groups, mine):      # a torch AdamW / FusedAdamW checkpoint has neither key
+            for k, v in kept.items():
+                group.setdefault(k, v)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = _closure_loss(closure)
+        self._refuse_step_while_swapped()
+        _check_ema_decay(self.ema_decay)
+        _check_max_grad_norm(self.max_grad_norm)
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not params or (self.max_grad_norm is not None and self._clip_grads(params)):
+            return loss
+        self._ratios = {}
+        for group in self.param_groups:
+            _check_lamb_flags(group)
+            (b1, b2), lr, eps, wd = group["betas"], group["lr"], group["eps"], group["weight_decay"]
+            adapt = wd != 0 or group["always_adapt"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("Lamb does not support sparse gradients")
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    st["step"] = torch.tensor(0.0)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if self.ema_decay is not None and "ema" not in st:
+                    st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
+                st["step"] += 1
+                t = int(float(st["step"]))
+                m, v, g = st["exp_avg"], st["exp_avg_sq"], p.grad
+                m.mul_(b1).add_(g, alpha=1.0 - b1)
+                v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+                u = (m / (1.0 - b1 ** t)) / (v.sqrt() / math.sqrt(1.0 - b2 ** t) + eps)
+                if wd != 0:
+                    u = u.add(p, alpha=wd)
+                r = torch.ones((), dtype=p.dtype, device=p.device)
+                if adapt:
+                    wn, un = torch.linalg.vector_norm(p), torch.linalg.vector_norm(u)
+                    r = torch.where((wn > 0) & (un > 0), wn / un, r)
+                if group["trust_clip"]:
+                    r = r.clamp(max=1.0)
+                p.add_(u * r, alpha=-lr)
+                self._ratios[p] = r
+                if self.ema_decay is not None:
+                    e = st["ema"]
+                    e.add_(p - e, alpha=1.0 - float(self.ema_decay))
+        return loss
+
+    def trust_ratios(self):
+        """{parameter: its trust ratio in the last step} as fresh 0-d tensors, as FusedLamb.trust_ratios()."""
+        return {p: r.clone() for p, r in self._ratios.items()}
+
+    swap_ema = EmaAdamW.swap_ema
+
+
+def param_groups_weight_decay(model, weight_decay, no_decay=("cls_tkn_embd", "pos_embd")):
+    """timm's split of a model's trainable parameters into two `param_groups`: `weight_decay = 0` for every parameter
+    with `ndim <= 1`, every one whose name ends in ".bias", and every one named in `no_decay` (by its full name or by
+    the last component of it, so "pos_embd" names "emdeddings.pos_embd"); `weight_decay` for everything else.
+    Parameters with requires_grad off are left out.  LAMB's rule for `weight_decay == 0` tensors (no trust ratio)
+    only bites where biases and norm weights sit in such a group; nothing calls this unless asked to."""
+    decay, plain = [], []
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        listed = name in no_decay or name.rsplit(".", 1)[-1] in no_decay
+        (plain if p.ndim <= 1 or name.endswith(".bias") or listed else decay).append(p)
+    return [{"params": plain, "weight_decay": 0.0}, {"params": decay, "weight_decay": weight_decay}]
+
+
 def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda", max_grad_norm=None, skip_nonfinite=True,
-                   ema_decay=None):
+                   ema_decay=None, opt="adamw", always_adapt=False, trust_clip=False):
     """The reference's optimizer (train.py:66, AdamW(lr, weight_decay=1e-4)): FusedAdamW on a ROCm device,
     torch.optim.AdamW on the host path.  `max_grad_norm` (not in the reference) clips by global gradient norm inside
     the step: FusedAdamW's own keyword on the device, ClippedAdamW on the host.  `ema_decay` (not in the reference
-    either) keeps an EMA of the weights inside the step: FusedAdamW's keyword on the device, EmaAdamW on the host."""
+    either) keeps an EMA of the weights inside the step: FusedAdamW's keyword on the device, EmaAdamW on the host.
+    `opt="lamb"` (not in the reference) gives FusedLamb on the device and Lamb on the host, with `always_adapt` and
+    `trust_clip` as their group defaults; `params` may be param_groups_weight_decay()'s groups."""
+    if opt not in ("adamw", "lamb"):
+        raise ValueError(f"opt must be 'adamw' or 'lamb' (got {opt!r})")
+    if opt == "lamb":
+        cls = Lamb if torch.device(device).type == "cpu" else FusedLamb
+        return cls(params, lr=lr, weight_decay=weight_decay, always_adapt=always_adapt, trust_clip=trust_clip,
+                   max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+    if always_adapt or trust_clip:
+        raise ValueError("always_adapt and trust_clip belong to opt='lamb'")
     if torch.device(device).type == "cpu":
         if ema_decay is not None:
             return EmaAdamW(params, ema_decay, max_grad_norm, skip_nonfinite, lr=lr, weight_decay=weight_decay)

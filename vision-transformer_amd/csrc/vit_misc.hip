@@ -611,6 +611,112 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(const vit_tensor_chunk* _
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// LAMB (vit_hip.h "LAMB"): Adam's moments, the update u = m_hat / (sqrt(v_hat) + eps) + wd * p, one trust ratio
+// |p| / |u| per tensor, then p -= lr * ratio * u.  The ratio needs the whole tensor's norms before any element of it
+// moves, so the step is two passes over the chunk table with a per-tensor finish between them.  u is not stored:
+// pass 2 forms it again from the m and v pass 1 wrote and the p it left alone (42 B per element over both passes;
+// storing u would cost 46 B and a parameter-sized buffer).
+// ---------------------------------------------------------------------------------------------------------------
+// u as both passes form it.  The host folds the bias corrections into c1 = bc1 / sqrt(bc2) and c2 = bc1 * eps, so
+// that (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) = m / (sqrt(v) * c1 + c2): five roundings (sqrt, c1, the fma, the
+// quotient, the last fma).  Both fused multiply-adds are spelled out, as in adamw_chunk and for its reason: left to
+// the compiler, what it fuses depends on the code around the call, and the two passes must form the same bits.
+VIT_DEV float lamb_u(float m, float v, float p, float c1, float c2, float wd) {
+  const float denom = __builtin_fmaf(sqrtf(v), c1, c2);
+  return __builtin_fmaf(wd, p, m / denom);
+}
+
+// Pass 1, one workgroup per chunk: m and v as adamw_chunk forms them, written back; partial[2i] = sum p^2 and
+// partial[2i + 1] = sum u^2 over chunk i, each fp32 value squared and added in fp64, a lane's elements in index
+// order, then block_sum_f64's fixed tree.  p is only read.  clip as in adamw_ema_kernel.
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const vit_tensor_chunk* __restrict__ tab, float b1, float b2,
+                                                           float c1, float c2, float wd, float gscale,
+                                                           const float* __restrict__ clip,
+                                                           double* __restrict__ partial) {
+  __shared__ double red_p[4], red_u[4];
+  if (clip) {
+    if (clip[2] != 0.f) return;
+    gscale = gscale * clip[1];
+  }
+  const vit_tensor_chunk ch = tab[blockIdx.x];
+  double sp = 0.0, su = 0.0;
+  for (int64_t t = threadIdx.x; t < ch.n; t += 256) {
+    const float g = ch.g[t] * gscale;
+    float m = ch.m[t], v = ch.v[t];
+    const float p = ch.p[t];
+    m = __builtin_fmaf(b1, m, (1.0f - b1) * g);
+    v = __builtin_fmaf(b2, v, (1.0f - b2) * g * g);
+    const float u = lamb_u(m, v, p, c1, c2, wd);
+    ch.m[t] = m;
+    ch.v[t] = v;
+    sp += (double)p * (double)p;
+    su += (double)u * (double)u;
+  }
+  sp = block_sum_f64(sp, red_p);
+  su = block_sum_f64(su, red_u);
+  if (threadIdx.x == 0) {
+    partial[2 * (int64_t)blockIdx.x] = sp;
+    partial[2 * (int64_t)blockIdx.x + 1] = su;
+  }
+}
+
+// One workgroup per tensor: its chunks are first[b] .. first[b + 1] - 1 of pass 1's table.  Thread i adds partials
+// first + i, first + i + 256, ... in that order, then the fixed tree, as grad_clip_finish_kernel does, so a tensor
+// of more than 256 chunks takes the same path.  trust[b] = |p| / |u| where `adapt` is set and both norms are positive,
+// else 1; at most 1 with `trust_clip`.  The quotient is formed in fp64 and rounded to fp32 once.
+__global__ __launch_bounds__(256) void lamb_trust_kernel(const double* __restrict__ partial,
+                                                         const int32_t* __restrict__ first, int adapt, int trust_clip,
+                                                         float* __restrict__ trust, const float* __restrict__ clip) {
+  __shared__ double red_p[4], red_u[4];
+  if (clip && clip[2] != 0.f) return;
+  const int64_t lo = first[blockIdx.x], hi = first[blockIdx.x + 1];
+  double sp = 0.0, su = 0.0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+    sp += partial[2 * i];
+    su += partial[2 * i + 1];
+  }
+  sp = block_sum_f64(sp, red_p);
+  su = block_sum_f64(su, red_u);
+  if (threadIdx.x != 0) return;
+  float r = 1.f;
+  if (adapt && sp > 0.0 && su > 0.0) r = (float)(sqrt(sp) / sqrt(su));      // a NaN sum compares false: r stays 1
+  if (trust_clip && r > 1.f) r = 1.f;
+  trust[blockIdx.x] = r;
+}
+
+// Pass 2, one workgroup per chunk: p -= (lr * trust[tensor of the chunk]) * u with u formed again by lamb_u, the
+// shadow, and with EMA the recurrence of adamw_chunk's EMA form on the chunk's EMA slice.
+template <class TS, bool EMA>
+VIT_DEV void lamb_update_chunk(const vit_tensor_chunk ch, float step, float c1, float c2, float wd,
+                               float* ema = nullptr, float ema_w = 0.f) {
+  for (int64_t t = threadIdx.x; t < ch.n; t += 256) {
+    const float m = ch.m[t], v = ch.v[t];
+    float p = ch.p[t];
+    float e = 0.f;
+    if constexpr (EMA) e = ema[t];
+    p = __builtin_fmaf(-step, lamb_u(m, v, p, c1, c2, wd), p);
+    ch.p[t] = p;
+    if constexpr (EMA) ema[t] = __builtin_fmaf(ema_w, p - e, e);
+    if (ch.shadow) st1<TS>((TS*)ch.shadow + t, p);
+  }
+}
+
+template <class TS>
+__global__ __launch_bounds__(256) void lamb_update_kernel(const vit_tensor_chunk* __restrict__ tab,
+                                                          float* const* __restrict__ ema,
+                                                          const int32_t* __restrict__ tensor_of_chunk,
+                                                          const float* __restrict__ trust, float lr, float c1,
+                                                          float c2, float wd, float ema_w,
+                                                          const float* __restrict__ clip) {
+  if (clip && clip[2] != 0.f) return;
+  const vit_tensor_chunk ch = tab[blockIdx.x];
+  const float step = lr * trust[tensor_of_chunk[blockIdx.x]];
+  float* const ema_p = ema ? ema[blockIdx.x] : nullptr;
+  if (ema_p) lamb_update_chunk<TS, true>(ch, step, c1, c2, wd, ema_p, ema_w);
+  else lamb_update_chunk<TS, false>(ch, step, c1, c2, wd);
+}
+
 }  // namespace
 
 // ===============================================================================================================
@@ -925,6 +1031,57 @@ extern "C" int vit_ema_swap(const vit_tensor_chunk* table_dev, float* const* ema
   VIT_REQUIRE(table_dev && ema_dev && nchunks > 0, "vit_ema_swap: bad arguments");
   TABLE_LAUNCH(ema_swap_kernel, table_dev, ema_dev);
   return vit::check_launch("vit_ema_swap");
+}
+
+// What vit_lamb_moments and vit_lamb_update check alike, and the two constants lamb_u takes in place of the bias
+// corrections, formed in double and rounded once each.
+static int lamb_factors(const char* who, bool ptrs, int64_t nchunks, float eps, float bias_corr1, float bias_corr2,
+                        float* c1, float* c2) {
+  VIT_REQUIRE(ptrs, "%s: null pointer", who);
+  VIT_REQUIRE(nchunks > 0 && nchunks <= 0x3fffffff, "%s: nchunks must be positive (got %lld)", who,
+              (long long)nchunks);
+  VIT_REQUIRE(bias_corr1 > 0.f && bias_corr1 <= 1.f && bias_corr2 > 0.f && bias_corr2 <= 1.f,
+              "%s: bias corrections must lie in (0, 1] (got %g, %g)", who, (double)bias_corr1, (double)bias_corr2);
+  VIT_REQUIRE(eps >= 0.f, "%s: eps must not be negative (got %g)", who, (double)eps);
+  *c1 = (float)((double)bias_corr1 / sqrt((double)bias_corr2));
+  *c2 = (float)((double)bias_corr1 * (double)eps);
+  return VIT_OK;
+}
+
+extern "C" int vit_lamb_moments(const vit_tensor_chunk* table_dev, int64_t nchunks, float beta1, float beta2,
+                                float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
+                                const float* clip, double* partial, void* stream) {
+  float c1, c2;
+  if (int rc = lamb_factors("vit_lamb_moments", table_dev && partial, nchunks, eps, bias_corr1, bias_corr2, &c1, &c2))
+    return rc;
+  lamb_moments_kernel<<<(unsigned)nchunks, 256, 0, VIT_STREAM(stream)>>>(table_dev, beta1, beta2, c1, c2, weight_decay,
+                                                                         grad_scale, clip, partial);
+  return vit::check_launch("vit_lamb_moments");
+}
+
+extern "C" int vit_lamb_trust(const double* partial, const int32_t* tensor_first, int64_t ntensors, int32_t adapt,
+                              int32_t trust_clip, float* trust, const float* clip, void* stream) {
+  VIT_REQUIRE(partial && tensor_first && trust, "vit_lamb_trust: null pointer");
+  VIT_REQUIRE(ntensors > 0 && ntensors <= 0x3fffffff, "vit_lamb_trust: ntensors must be positive (got %lld)",
+              (long long)ntensors);
+  lamb_trust_kernel<<<(unsigned)ntensors, 256, 0, VIT_STREAM(stream)>>>(partial, tensor_first, adapt != 0,
+                                                                        trust_clip != 0, trust, clip);
+  return vit::check_launch("vit_lamb_trust");
+}
+
+extern "C" int vit_lamb_update(const vit_tensor_chunk* table_dev, float* const* ema_dev,
+                               const int32_t* tensor_of_chunk, const float* trust, int64_t nchunks, float lr,
+                               float eps, float weight_decay, float bias_corr1, float bias_corr2,
+                               int32_t shadow_dtype, float ema_weight, const float* clip, void* stream) {
+  float c1, c2;
+  if (int rc = lamb_factors("vit_lamb_update", table_dev && tensor_of_chunk && trust, nchunks, eps, bias_corr1,
+                            bias_corr2, &c1, &c2))
+    return rc;
+  VIT_REQUIRE(!ema_dev || (ema_weight > 0.f && ema_weight < 1.f),
+              "vit_lamb_update: ema_weight must lie in (0, 1) (got %g)", (double)ema_weight);
+  TABLE_LAUNCH(lamb_update_kernel, table_dev, ema_dev, tensor_of_chunk, trust, lr, c1, c2, weight_decay, ema_weight,
+               clip);
+  return vit::check_launch("vit_lamb_update");
 }
 
 extern "C" int vit_pack(const vit_tensor_chunk* table_dev, int64_t nchunks, int32_t shadow_dtype, void* stream) {

@@ -31,7 +31,7 @@ import torch
 import torch.distributed as dist
 
 from VisionTransformer import config, vit
-from VisionTransformer.optim import MixedLabels, cross_entropy, make_optimizer
+from VisionTransformer.optim import MixedLabels, cross_entropy, make_optimizer, param_groups_weight_decay
 
 device = "cuda" if torch.cuda.is_available() else "cpu"
 
@@ -192,9 +192,17 @@ def _rank_world():
     return 0, 1
 
 
+def _optimizer(model, lr, dev, opt="adamw", weight_decay=1e-4, no_decay_1d=False, **kw):
+    """make_optimizer over the model's parameters: one group as the reference has it, or with `no_decay_1d`
+    param_groups_weight_decay's two."""
+    params = param_groups_weight_decay(model, weight_decay) if no_decay_1d else model.parameters()
+    return make_optimizer(params, lr=lr, weight_decay=weight_decay, device=dev, opt=opt, **kw)
+
+
 def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkpoint_dir, lr=1e-4,
           log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None, ema_decay=None,
-          label_smoothing=0.0, mix=None):
+          label_smoothing=0.0, mix=None, opt="adamw", weight_decay=1e-4, no_decay_1d=False, always_adapt=False,
+          trust_clip=False):
     """The reference training loop (train.py:60-119) on the HIP path.  Returns the last epoch's summed loss.
 
     Defaults keep the GPU busy: no host sync inside the epoch — the epoch loss is summed on the device and the per-step
@@ -222,21 +230,26 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     MixedLabels (data.DeviceBatches(mix=...) stages the mix one batch ahead).  The logged "Loss/train_batch", the epoch
     loss and the checkpoint's "loss" are then the smoothed / mixed loss, not the hard-label cross entropy.  evaluate()
     and validation see unmixed data and hard labels.  Under data parallelism nothing more is needed: the mix is
-    per-rank input work before the forward, and BatchMix seeds itself per rank."""
+    per-rank input work before the forward, and BatchMix seeds itself per rank.
+
+    `opt`, `weight_decay`, `no_decay_1d`, `always_adapt`, `trust_clip` (not in the reference, which trains with
+    AdamW(weight_decay=1e-4) over one group, train.py:66): `opt="lamb"` steps with LAMB (optim.FusedLamb; Lamb on the
+    host path), `no_decay_1d` puts biases, norm weights and the two embeddings into a `weight_decay = 0` group
+    (optim.param_groups_weight_decay), and the two flags are LAMB's.  The checkpoint dict is the same either way."""
     rank, world = _rank_world()
     saved_epoch = search_checkpoint(checkpoint_dir)
     torch.manual_seed(0)                              # identical init on every rank
     model = vit.VisionTransformer(configs)
-    optimizer = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=device,
-                               max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+    opt_kw = dict(opt=opt, weight_decay=weight_decay, no_decay_1d=no_decay_1d, always_adapt=always_adapt,
+                  trust_clip=trust_clip, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+    optimizer = _optimizer(model, lr, device, **opt_kw)
     iteration = 0
     if saved_epoch is not None:
         print(f"Checkpoint Found. Loading model from epoch {saved_epoch}")
         ckpt = torch.load(os.path.join(checkpoint_dir, f"{saved_epoch}.pt"), map_location="cpu", weights_only=True)
         model.load_state_dict(ckpt["model_state_dict"])
         model = model.to(device)
-        optimizer = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=device,
-                                   max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+        optimizer = _optimizer(model, lr, device, **opt_kw)
         optimizer.load_state_dict(ckpt["optimizer_state_dict"])
         iteration = 0 if reference_loop else int(ckpt.get("step", 0))
     else:
@@ -324,17 +337,19 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
 
 
 def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None, ema_decay=None,
-               label_smoothing=0.0, mix=None):
+               label_smoothing=0.0, mix=None, opt="adamw", weight_decay=1e-4, no_decay_1d=False, always_adapt=False,
+               trust_clip=False):
     """The hot loop body (train.py:91-98: forward, CE loss, zero_grad(set_to_none), backward, AdamW step) on one
     synthetic batch already resident on `dev`, dropout on; returns (seconds per timed step, last loss).  This is the
     repo's own CPU training step that bench.py's `cpu_baseline` times (BASELINE config 1).  Unclipped unless
     `max_grad_norm` is given, and without a weight EMA unless `ema_decay` is.  With `mix` (a data.BatchMix) every step
-    first mixes the resident batch, and `label_smoothing` goes to the loss, as in train()."""
+    first mixes the resident batch, and `label_smoothing` goes to the loss, as in train().  `opt`, `weight_decay`,
+    `no_decay_1d`, `always_adapt` and `trust_clip` choose the optimizer as in train()."""
     dev = torch.device(dev or device)
     torch.manual_seed(0)
     model = vit.VisionTransformer(configs).to(dev).train()
-    opt = make_optimizer(model.parameters(), lr=lr, weight_decay=1e-4, device=dev, max_grad_norm=max_grad_norm,
-                         ema_decay=ema_decay)
+    opt = _optimizer(model, lr, dev, opt=opt, weight_decay=weight_decay, no_decay_1d=no_decay_1d,
+                     always_adapt=always_adapt, trust_clip=trust_clip, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
     g = torch.Generator().manual_seed(seed)
     n_img = int(round((configs.num_patches ** 0.5) * configs.patch_size))
     x = torch.randn(configs.batch_size, configs.input_channels, n_img, n_img, generator=g).to(dev)
@@ -375,6 +390,16 @@ def main():
     ap.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
                     help="keep an exponential moving average of the weights with this decay inside the optimizer "
                          "step, validate on it and save it as ema_state_dict (default: none, as the reference)")
+    ap.add_argument("--opt", default="adamw", choices=["adamw", "lamb"],
+                    help="optimizer: AdamW as the reference, or LAMB (per-tensor trust ratios, for large batches)")
+    ap.add_argument("--weight-decay", type=float, default=1e-4, metavar="F",
+                    help="decoupled weight decay (default 1e-4, the reference's)")
+    ap.add_argument("--no-decay-1d", action="store_true",
+                    help="no weight decay on biases, norm weights and the cls / position embeddings (timm's rule; "
+                         "default: every parameter decays, as the reference)")
+    ap.add_argument("--lamb-always-adapt", action="store_true",
+                    help="LAMB: apply the trust ratio to tensors without weight decay too")
+    ap.add_argument("--lamb-trust-clip", action="store_true", help="LAMB: bound every trust ratio by 1")
     ap.add_argument("--drop-path", type=float, default=0.0, metavar="RATE",
                     help="stochastic depth: drop each residual branch per image, block l of L at rate RATE * l / (L - 1) "
                          "(timm's linear rule; DeiT-B trains with 0.1; default 0: off, as the reference)")
@@ -453,10 +478,14 @@ def main():
         from VisionTransformer.data import TrainAugment
         augment = TrainAugment(scale=tuple(args.crop_scale) if args.random_resized_crop else None,
                                ratio=tuple(args.crop_ratio), hflip=args.hflip, erase_prob=args.random_erase)
+    if args.opt != "lamb" and (args.lamb_always_adapt or args.lamb_trust_clip):
+        ap.error("--lamb-always-adapt and --lamb-trust-clip need --opt lamb")
+    opt_args = dict(opt=args.opt, weight_decay=args.weight_decay, no_decay_1d=args.no_decay_1d,
+                    always_adapt=args.lamb_always_adapt, trust_clip=args.lamb_trust_clip)
     if args.bench:
         steps = args.steps or 30
         sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm,
-                               ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix)
+                               ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix, **opt_args)
         print(json.dumps({"device": device, "model": args.model, "img": args.img, "batch": args.batch,
                           "dtype": args.dtype, "threads": torch.get_num_threads(), "warmup": args.warmup,
                           "steps": steps, "ms_per_step": round(sec * 1e3, 3),
@@ -504,7 +533,7 @@ def main():
                                                   sampler=tsampler, drop_last=False, pin_memory=pin)
     train(cfg, train_loader, test_loader, args.epochs, args.eval_iter, args.log_dir, args.checkpoint_dir,
           lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop, max_grad_norm=args.clip_grad_norm,
-          ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix)
+          ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix, **opt_args)
     if world > 1:
         dist.destroy_process_group()
 
