@@ -79,7 +79,8 @@ const char* vit_last_error(void);
  * symbol (dlsym, or a link error).  The version changes only when an existing signature or meaning does.  Added under
  * 18 this way: vit_softmax_xent_mixed and vit_mix_batch (label smoothing, mixup and CutMix), with no option name;
  * vit_augment_workspace_bytes and vit_augment_to_tensor (crop, flip, normalize, erase), with "augment_path";
- * vit_drop_path_rows, vit_gemm_rowscale and vit_gemm_kernel_choice (stochastic depth), with no option name.
+ * vit_drop_path_rows, vit_gemm_rowscale and vit_gemm_kernel_choice (stochastic depth), with no option name;
+ * vit_adamw_groups and vit_lamb_{moments,trust,update}_groups (every param group in one launch), with no option name.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -519,6 +520,52 @@ int vit_lamb_trust(const double* partial /* [2 * nchunks] */, const int32_t* ten
 int vit_lamb_update(const vit_tensor_chunk* table_dev, float* const* ema_dev, const int32_t* tensor_of_chunk,
                     const float* trust, int64_t nchunks, float lr, float eps, float weight_decay, float bias_corr1,
                     float bias_corr2, int32_t shadow_dtype, float ema_weight, const float* clip, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Grouped optimizer steps: the AdamW and LAMB updates above over the chunks of up to VIT_OPT_MAX_GROUPS param groups
+ * in ONE launch each (purely added entry points, ABI 18).  With layer-wise learning-rate decay a ViT-B has 28 groups
+ * (14 depth levels x {decay, no decay}); stepping them one launch per group gives 28 (AdamW) or 84 (LAMB) launches of
+ * a handful of chunks each.  Here the table holds the chunks of every group and a device array names each chunk's
+ * group; the groups' hyper-parameters are HOST memory, read during the call, turned into the factors the
+ * single-group entry points form (the same floats) and passed to the kernel by value in its argument segment: a
+ * learning rate that changes every step costs no copy and no staging buffer.
+ *   group_of_chunk[i] (device, int32 [nchunks]) is the index into groups[] of chunk i; chunks of one group need not
+ *   be consecutive.  A chunk whose index is not in 0..ngroups-1 is left untouched (so is a tensor of
+ *   vit_lamb_trust_groups whose group_of_tensor entry is not).
+ *   vit_adamw_groups: every chunk comes out bit for bit as from vit_adamw (clip == NULL, ema_dev == NULL),
+ *     vit_adamw_clipped (clip) or vit_adamw_ema (ema_dev; a NULL ema_dev[i] keeps no EMA for chunk i) called with its
+ *     group's scalars.  flags must be 0.
+ *   vit_lamb_*_groups: the three LAMB passes; p, m, v, the shadows, the EMA, the partials and trust[] are bit for bit
+ *     those of per-group calls.  group_of_tensor (device, int32 [ntensors]) gives the trust pass each tensor's group;
+ *     VIT_OPT_ADAPT and VIT_OPT_TRUST_CLIP are vit_lamb_trust's `adapt` and `trust_clip`.  All three take the same
+ *     groups[].
+ * Refused (VIT_ERR_INVALID): NULL pointers (ema_dev and clip may be NULL), a count <= 0, ngroups outside
+ * 1..VIT_OPT_MAX_GROUPS, a bias correction outside (0, 1], a negative eps, an lr that is not finite, flags other than
+ * the two above (any flag for vit_adamw_groups), and with ema_dev an ema_weight outside (0, 1).
+ * ------------------------------------------------------------------------------------------------------------ */
+#define VIT_OPT_MAX_GROUPS 64
+#define VIT_OPT_ADAPT 1      /* LAMB: trust ratio applies (wd != 0 or always_adapt) */
+#define VIT_OPT_TRUST_CLIP 2 /* LAMB: min(r, 1) */
+typedef struct vit_opt_group { /* 32 bytes, host memory */
+  float lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2;
+  int32_t flags; /* AdamW entry point: must be 0 */
+} vit_opt_group;
+
+int vit_adamw_groups(const vit_tensor_chunk* table_dev, float* const* ema_dev /* or NULL */,
+                     const int32_t* group_of_chunk /* device [nchunks] */, int64_t nchunks,
+                     const vit_opt_group* groups /* host [ngroups] */, int32_t ngroups, float grad_scale,
+                     int32_t shadow_dtype, float ema_weight, const float* clip /* or NULL */, void* stream);
+int vit_lamb_moments_groups(const vit_tensor_chunk* table_dev, const int32_t* group_of_chunk, int64_t nchunks,
+                            const vit_opt_group* groups, int32_t ngroups, float grad_scale, const float* clip,
+                            double* partial /* [2 * nchunks] */, void* stream);
+int vit_lamb_trust_groups(const double* partial, const int32_t* tensor_first /* [ntensors + 1] */,
+                          const int32_t* group_of_tensor /* device [ntensors] */, int64_t ntensors,
+                          const vit_opt_group* groups, int32_t ngroups, float* trust /* [ntensors] */,
+                          const float* clip, void* stream);
+int vit_lamb_update_groups(const vit_tensor_chunk* table_dev, float* const* ema_dev, const int32_t* tensor_of_chunk,
+                           const float* trust, const int32_t* group_of_chunk, int64_t nchunks,
+                           const vit_opt_group* groups, int32_t ngroups, int32_t shadow_dtype, float ema_weight,
+                           const float* clip, void* stream);
 
 #ifdef __cplusplus
 }

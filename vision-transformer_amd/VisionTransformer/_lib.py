@@ -61,6 +61,13 @@ class AugItem(ctypes.Structure):      # vit_aug_item, 36 bytes
     _fields_ = [(n, ctypes.c_int32) for n in ("x0", "y0", "cw", "ch", "flip", "ey0", "ey1", "ex0", "ex1")]
 
 
+class OptGroup(ctypes.Structure):     # vit_opt_group, 32 bytes, host memory
+    _fields_ = [(n, ctypes.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "bias_corr1",
+                                              "bias_corr2")] + [("flags", ctypes.c_int32)]
+
+
+OPT_MAX_GROUPS, OPT_ADAPT, OPT_TRUST_CLIP = 64, 1, 2      # VIT_OPT_* (vit_hip.h)
+
 # the tiled form of vit_augment_to_tensor (vit_hip.h VIT_AUG_TILE_*): tile rows x columns, most source rows of a tile
 AUG_TILE_ROWS, AUG_TILE_COLS, AUG_TILE_MAX_SPAN = 16, 64, 80
 
@@ -121,6 +128,11 @@ _SIGS = {
     "vit_lamb_moments": (ctypes.c_int, [_P, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "vit_lamb_trust": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P]),
     "vit_lamb_update": (ctypes.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I32, _F, _P, _P]),
+    "vit_adamw_groups": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(OptGroup), _I32, _F, _I32, _F, _P, _P]),
+    "vit_lamb_moments_groups": (ctypes.c_int, [_P, _P, _I64, ctypes.POINTER(OptGroup), _I32, _F, _P, _P, _P]),
+    "vit_lamb_trust_groups": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(OptGroup), _I32, _P, _P, _P]),
+    "vit_lamb_update_groups": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, ctypes.POINTER(OptGroup), _I32, _I32, _F,
+                                              _P, _P]),
 }
 
 EPI_BDR, EPI_SLAB, EPI_GENERAL, EPI_BDRS = 3, 4, 5, 8    # VIT_EPI_* (vit_hip.h): kinds vit_gemm_kernel_choice reports

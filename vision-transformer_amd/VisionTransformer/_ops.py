@@ -2,6 +2,7 @@
 (or `stream`) and returns immediately.  Shapes/dtypes are validated on the host; the kernels re-validate."""
 import ctypes
 import os
+import struct
 
 import numpy as np
 import torch
@@ -722,3 +723,104 @@ def lamb_update(table_dev, tensor_of_chunk, trust, nchunks, lr, eps, weight_deca
         _check_clip(clip)
     _lib.call("vit_lamb_update", _ptr(table_dev), _ptr(ema_dev), _ptr(tensor_of_chunk), _ptr(trust), nchunks, lr, eps,
               weight_decay, bias_corr1, bias_corr2, dtype_code(shadow_dtype), ema_w, _ptr(clip), _stream(stream))
+
+
+# ---- grouped steps (vit_hip.h "Grouped optimizer steps") -----------------------------------------------------------
+def build_group_index(entries, sizes, device):
+    """The group maps that go with build_chunk_table(entries) and build_tensor_index(entries), cut by the same
+    _chunks(): `entries` holds the tensors of group 0, then those of group 1, ... and `sizes[k]` is how many belong to
+    group k.  Returns (group_of_chunk int32 [nchunks], group_of_tensor int32 [ntensors]) on `device`, and `bounds`, a
+    host list of (first tensor, first chunk) per group with (ntensors, nchunks) last.  The indices are taken modulo
+    OPT_MAX_GROUPS, so that a launch over groups [64 k, 64 k + 64) can hand the kernel those 64 alone."""
+    if sum(sizes) != len(entries):
+        raise ValueError("sizes must add up to the number of entries")
+    of_chunk, of_tensor, bounds, it = [], [], [], iter(entries)
+    for k, size in enumerate(sizes):
+        bounds.append((len(of_tensor), len(of_chunk)))
+        for _ in range(size):
+            of_tensor.append(k % _lib.OPT_MAX_GROUPS)
+            of_chunk.extend([k % _lib.OPT_MAX_GROUPS] * len(_chunks(next(it)[0].numel())))
+    bounds.append((len(of_tensor), len(of_chunk)))
+    return (torch.tensor(of_chunk, dtype=torch.int32).to(device), torch.tensor(of_tensor, dtype=torch.int32).to(device),
+            bounds)
+
+
+def opt_groups(specs):
+    """The host vit_opt_group array of `specs`: (lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, flags)
+    per group, the floats rounded to fp32 as a `float` argument of the single-group entry points is."""
+    if not 1 <= len(specs) <= _lib.OPT_MAX_GROUPS:
+        raise ValueError(f"a grouped launch takes 1..{_lib.OPT_MAX_GROUPS} groups (got {len(specs)})")
+    packed = struct.pack("7fi" * len(specs), *[x for s in specs for x in s])      # one call, not one object per field
+    return (_lib.OptGroup * len(specs)).from_buffer_copy(packed)
+
+
+def _check_group_index(t, numel, what):
+    _check_lamb_buffer(t, torch.int32, numel, what)
+    if t.numel() != numel:
+        raise ValueError(f"{what} must have {numel} elements")
+
+
+def adamw_groups(table_dev, group_of_chunk, nchunks, specs, grad_scale, shadow_dtype, ema_dev=None, ema_decay=None,
+                 stream=None, clip=None):
+    """vit_adamw_groups: adamw() / adamw_ema() over the chunks of several groups in one launch; chunk i takes the
+    scalars of specs[group_of_chunk[i]] (opt_groups).  `ema_dev` / `ema_decay` and `clip` as in adamw_ema()."""
+    _need_cuda(table_dev)
+    _check_group_index(group_of_chunk, nchunks, "group_of_chunk")
+    ema_w = 0.0
+    if ema_dev is not None:
+        _check_ema(ema_dev, nchunks)
+        ema_w = 1.0 - float(ema_decay)
+    if clip is not None:
+        _check_clip(clip)
+    groups = opt_groups(specs)
+    _lib.call("vit_adamw_groups", _ptr(table_dev), _ptr(ema_dev), _ptr(group_of_chunk), nchunks, groups, len(groups),
+              grad_scale, dtype_code(shadow_dtype), ema_w, _ptr(clip), _stream(stream))
+
+
+def lamb_moments_groups(table_dev, group_of_chunk, nchunks, specs, grad_scale, partial, stream=None, clip=None):
+    """vit_lamb_moments_groups: lamb_moments() with each chunk's scalars from specs[group_of_chunk[i]]."""
+    _need_cuda(table_dev)
+    _check_group_index(group_of_chunk, nchunks, "group_of_chunk")
+    _check_lamb_buffer(partial, torch.float64, 2 * nchunks, "partial")
+    if clip is not None:
+        _check_clip(clip)
+    groups = opt_groups(specs)
+    _lib.call("vit_lamb_moments_groups", _ptr(table_dev), _ptr(group_of_chunk), nchunks, groups, len(groups),
+              grad_scale, _ptr(clip), _ptr(partial), _stream(stream))
+
+
+def lamb_trust_groups(partial, tensor_first, group_of_tensor, ntensors, specs, trust, stream=None, clip=None):
+    """vit_lamb_trust_groups: lamb_trust() with each tensor's flags from specs[group_of_tensor[i]]."""
+    _check_lamb_buffer(tensor_first, torch.int32, ntensors + 1, "tensor_first")
+    if tensor_first.numel() != ntensors + 1:
+        raise ValueError(f"tensor_first must have ntensors + 1 = {ntensors + 1} elements")
+    _check_group_index(group_of_tensor, ntensors, "group_of_tensor")
+    _check_lamb_buffer(trust, torch.float32, ntensors, "trust")
+    if partial is None or partial.dtype != torch.float64 or not partial.is_contiguous():
+        raise ValueError("partial must be a contiguous float64 device tensor")
+    _need_cuda(partial)
+    if clip is not None:
+        _check_clip(clip)
+    groups = opt_groups(specs)
+    _lib.call("vit_lamb_trust_groups", _ptr(partial), _ptr(tensor_first), _ptr(group_of_tensor), ntensors, groups,
+              len(groups), _ptr(trust), _ptr(clip), _stream(stream))
+
+
+def lamb_update_groups(table_dev, tensor_of_chunk, trust, group_of_chunk, nchunks, specs, shadow_dtype, ema_dev=None,
+                       ema_decay=None, stream=None, clip=None):
+    """vit_lamb_update_groups: lamb_update() with each chunk's scalars from specs[group_of_chunk[i]], the specs
+    lamb_moments_groups was given."""
+    _need_cuda(table_dev)
+    _check_group_index(tensor_of_chunk, nchunks, "tensor_of_chunk")
+    _check_group_index(group_of_chunk, nchunks, "group_of_chunk")
+    _check_lamb_buffer(trust, torch.float32, 1, "trust")
+    ema_w = 0.0
+    if ema_dev is not None:
+        _check_ema(ema_dev, nchunks)
+        ema_w = 1.0 - float(ema_decay)
+    if clip is not None:
+        _check_clip(clip)
+    groups = opt_groups(specs)
+    _lib.call("vit_lamb_update_groups", _ptr(table_dev), _ptr(ema_dev), _ptr(tensor_of_chunk), _ptr(trust),
+              _ptr(group_of_chunk), nchunks, groups, len(groups), dtype_code(shadow_dtype), ema_w, _ptr(clip),
+              _stream(stream))

@@ -11,6 +11,7 @@ and / or MixedLabels (mixup / CutMix) the same against a smoothed two-label targ
 """
 import collections
 import contextlib
+import ctypes
 import math
 import struct
 import typing
@@ -135,6 +136,44 @@ class _StepTable:
         return True
 
 
+class _GroupedTable(_StepTable):
+    """The merged table of a `fuse_groups` step: the stepping parameters of every group, each group's consecutive, in
+    one chunk table, with the device maps chunk -> group and tensor -> group beside it (indices modulo
+    _lib.OPT_MAX_GROUPS) and `spans`, one _Span per launch of at most that many groups.  `sizes` is how many
+    parameters each group brought: with valid(), which holds unchanged, it tells that the table still describes the
+    step.  No hyper-parameter is part of it."""
+
+    __slots__ = ("sizes", "group_of_chunk", "group_of_tensor", "spans")
+
+    @classmethod
+    def build_grouped(cls, opt, ps, sizes):
+        tab = cls.build(opt, ps)
+        tab.sizes = list(sizes)
+        tab.group_of_chunk, tab.group_of_tensor, bounds = _ops.build_group_index(tab.keep, sizes, tab.device)
+        if bounds[-1][1] != tab.nchunks:
+            raise RuntimeError("FusedAdamW: the group index disagrees with the chunk table")
+        cap, size = _ops._lib.OPT_MAX_GROUPS, ctypes.sizeof(_ops._lib.TensorChunk)
+        tab.spans = []
+        for g0 in range(0, len(sizes), cap):
+            g1 = min(g0 + cap, len(sizes))
+            (t0, c0), (t1, c1) = bounds[g0], bounds[g1]
+            if c1 > c0:
+                tab.spans.append(_Span(g0, g1, c0, c1, t0, t1, tab.dev_tab[c0 * size:c1 * size],
+                                       tab.group_of_chunk[c0:c1],
+                                       tab.ema_dev[c0:c1] if tab.ema_dev is not None else None))
+        return tab
+
+    @staticmethod
+    def fusable(ps):
+        """One device and one shadow dtype over `ps`: what one launch can serve."""
+        if len({p.device for p in ps}) != 1:
+            return False
+        return len({s.dtype for s in map(shadow_of, ps) if s is not None}) <= 1
+
+
+# groups [g0, g1) of a merged table: its chunks [c0, c1) and tensors [t0, t1), and the slices of the chunk table, of
+# group_of_chunk and of the EMA pointers (None without) that one launch over them takes
+_Span = collections.namedtuple("_Span", "g0 g1 c0 c1 t0 t1 rows group_of_chunk ema_dev")
 # tensor_first int32 [ntensors + 1], tensor_of_chunk int32 [nchunks], the fp64 [2 * nchunks] norm partials, the fp32
 # [ntensors] trust ratios (ones until a step writes them): all on the table's device, sized once; `chunk` is the
 # _ops.CHUNK they were cut with
@@ -207,14 +246,24 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
     EMA in place, shadows included, so the fused engine evaluates the EMA with no repack and no rebuild;
     `ema_weights()` is the context manager around it (step() raises inside), and `ema_state_dict(model)` reads the
     EMA out without swapping.  Data parallel needs nothing more: every rank holds bitwise the same gradients after
-    the all-reduce, hence the same weights and the same EMA."""
+    the all-reduce, hence the same weights and the same EMA.
+
+    `fuse_groups` (off by default; an attribute, not a `param_groups` key).  step() launches once per param group,
+    which is one launch for the reference's single group and 28 for a ViT-B under layer-wise learning-rate decay
+    (param_groups_layer_decay).  With `fuse_groups` every group goes in ONE launch (one per 64 groups): a merged chunk
+    table under the key ("groups", "all"), each chunk naming its group, and the groups' hyper-parameters, read from
+    `param_groups` at every step, passed to the kernel by value (include/vit_hip.h "Grouped optimizer steps"), so a
+    scheduler that rewrites `group["lr"]` every step rebuilds nothing and copies nothing.  Bit for bit the per-group
+    step.  A step in which some group holds parameters at different step counts (a parameter whose first gradient
+    came late), or whose parameters span devices or shadow dtypes, runs per group as with `fuse_groups` off."""
 
     # its kernel writes the engines' compute-dtype shadows along with the masters: no repack follows a step
     # (_engine._after_optimizer_step marks them stale after every other optimizer's)
     refreshes_shadows = True
+    fuse_groups = False       # the instance's keyword; here for an optimizer unpickled from before it existed
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
-                 max_grad_norm=None, skip_nonfinite=True, ema_decay=None):
+                 max_grad_norm=None, skip_nonfinite=True, ema_decay=None, fuse_groups=False):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid AdamW hyper-parameters")
         _check_max_grad_norm(max_grad_norm)
@@ -222,6 +271,7 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
         self._version = 0
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = grad_scale
+        self.fuse_groups = fuse_groups
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = skip_nonfinite
         self.ema_decay = ema_decay
@@ -357,6 +407,9 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
         loss = _closure_loss(closure)
         self._refuse_step_while_swapped()
         _check_ema_decay(self.ema_decay)
+        if self.fuse_groups:
+            self._step_grouped()
+            return loss
         ema, clipped, work = self.ema_decay is not None, self.max_grad_norm is not None, []
         for gi, group in enumerate(self.param_groups):
             ps_all = group["params"]
@@ -376,6 +429,76 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
         if work:
             self._clipped_launch(work)
         return loss
+
+    # ---- fuse_groups: every group in one launch ------------------------------------------------------------------
+    def _step_grouped(self):
+        """step() with `fuse_groups`: state and counters as ever, then one merged table over every group and one
+        grouped launch per _lib.OPT_MAX_GROUPS groups, where every group's stepping parameters share a step count
+        and all of them one device and one shadow dtype; else this step goes per group, as with `fuse_groups` off."""
+        ema, clipped, plan = self.ema_decay is not None, self.max_grad_norm is not None, []
+        for gi, group in enumerate(self.param_groups):
+            ps_all = group["params"]
+            idx = [i for i, p in enumerate(ps_all) if p.grad is not None]
+            if not idx:
+                continue
+            if self._make_state([ps_all[i] for i in idx], ema):
+                self.invalidate()
+            plan.append((gi, group, self._advance(gi, group, idx)))
+        if not plan:
+            return
+        tab = self._grouped_table(plan) if all(len(by_step) == 1 for _, _, by_step in plan) else None
+        if tab is None:
+            work = []
+            for gi, group, by_step in plan:
+                for t, ps in by_step.items():
+                    t_tab = self._table((gi, "all") if len(by_step) == 1 else (gi, "t", t), ps)
+                    if clipped:
+                        work.append((t_tab, group, t))
+                    else:
+                        self._adamw(t_tab, group, t)
+            if work:
+                self._clipped_launch(work)
+            return
+        clip = None
+        if clipped:      # the merged table lists the chunks in the order the per-group tables would: the same partials
+            _check_max_grad_norm(self.max_grad_norm)
+            if self._partial is None or self._partial.device != tab.device or self._partial.numel() < tab.nchunks:
+                self._partial = torch.empty(tab.nchunks, dtype=torch.float64, device=tab.device)
+            clip = self._clip_state(tab.device)
+            _ops.grad_sumsq(tab.dev_tab, tab.nchunks, self.grad_scale, self._partial[:tab.nchunks])
+            _ops.grad_clip_finish(self._partial, tab.nchunks, self.max_grad_norm, clip, self.skip_nonfinite)
+        specs = [self._group_spec(group, next(iter(by_step))) for _, group, by_step in plan]
+        for span in tab.spans:
+            self._grouped_launch(tab, specs[span.g0:span.g1], span, clip)
+
+    def _grouped_table(self, plan):
+        """The merged table of `plan` (cached under its own key, valid as any _StepTable is and while each group brings
+        as many parameters as it did), or None where one launch cannot serve its parameters."""
+        ps = [p for _, _, by_step in plan for p in next(iter(by_step.values()))]
+        sizes = [len(next(iter(by_step.values()))) for _, _, by_step in plan]
+        key = ("groups", "all")
+        old = self._tables.get(key)
+        if old is not None and old.sizes == sizes and old.valid(self, ps):
+            return old
+        if not _GroupedTable.fusable(ps):
+            return None
+        tab = self._tables[key] = _GroupedTable.build_grouped(self, ps, sizes)
+        # as FusedLamb._table: the same parameters cut alike keep the tensor index, its buffers and the last ratios
+        if (old is not None and old.lamb is not None and old.lamb.chunk == _ops.CHUNK and tab.device == old.device
+                and len(old.params) == len(ps) and all(a is b for a, b in zip(old.params, ps))):
+            tab.lamb = old.lamb
+        return tab
+
+    def _group_spec(self, group, t):
+        """A group's vit_opt_group at step count `t`: the scalars _adamw() passes."""
+        b1, b2 = group["betas"]
+        return (group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t, 0)
+
+    def _grouped_launch(self, tab, specs, span, clip):
+        """The update of one span of the merged table, whose groups are those of `specs`."""
+        ema = self.ema_decay is not None
+        _ops.adamw_groups(span.rows, span.group_of_chunk, span.c1 - span.c0, specs, self.grad_scale, tab.shadow_dtype,
+                          ema_dev=span.ema_dev if ema else None, ema_decay=self.ema_decay if ema else None, clip=clip)
 
     # ---- weight EMA ---------------------------------------------------------------------------------------------
     def _ema_params(self):
@@ -436,11 +559,13 @@ class FusedLamb(FusedAdamW):
     ratios without a sync."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, always_adapt=False,
-                 trust_clip=False, grad_scale=1.0, max_grad_norm=None, skip_nonfinite=True, ema_decay=None):
+                 trust_clip=False, grad_scale=1.0, max_grad_norm=None, skip_nonfinite=True, ema_decay=None,
+                 fuse_groups=False):
         flags = dict(always_adapt=always_adapt, trust_clip=trust_clip)
         _check_lamb_flags(flags)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
-                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
+                         fuse_groups=fuse_groups)
         self.defaults.update(flags)
         for group in self.param_groups:
             for k, v in flags.items():
@@ -489,6 +614,30 @@ class FusedLamb(FusedAdamW):
                          tab.shadow_dtype, ema_dev=tab.ema_dev if ema else None,
                          ema_decay=self.ema_decay if ema else None, clip=clip)
         self._stepped.append(tab)
+
+    def _group_spec(self, group, t):
+        """A group's vit_opt_group at step count `t`: the scalars _adamw() passes, the betas rounded as there."""
+        _check_lamb_flags(group)
+        b1, b2 = (_as_f32(b) for b in group["betas"])
+        wd = group["weight_decay"]
+        flags = ((_ops._lib.OPT_ADAPT if wd != 0 or group["always_adapt"] else 0)
+                 | (_ops._lib.OPT_TRUST_CLIP if group["trust_clip"] else 0))
+        return (group["lr"], b1, b2, group["eps"], wd, 1.0 - b1 ** t, 1.0 - b2 ** t, flags)
+
+    def _grouped_launch(self, tab, specs, span, clip):
+        """The three LAMB launches over one span of the merged table.  The partials, the tensor index and the ratios
+        are the whole table's: the slices keep their absolute indices."""
+        c0, c1, t0, t1, rows, of_chunk = span.c0, span.c1, span.t0, span.t1, span.rows, span.group_of_chunk
+        ix = tab.lamb_index()
+        ema = self.ema_decay is not None
+        _ops.lamb_moments_groups(rows, of_chunk, c1 - c0, specs, self.grad_scale, ix.partial[2 * c0:2 * c1], clip=clip)
+        _ops.lamb_trust_groups(ix.partial, ix.tensor_first[t0:t1 + 1], tab.group_of_tensor[t0:t1], t1 - t0, specs,
+                               ix.trust[t0:t1], clip=clip)
+        _ops.lamb_update_groups(rows, ix.tensor_of_chunk[c0:c1], ix.trust, of_chunk, c1 - c0, specs, tab.shadow_dtype,
+                                ema_dev=span.ema_dev if ema else None,
+                                ema_decay=self.ema_decay if ema else None, clip=clip)
+        if not self._stepped or self._stepped[-1] is not tab:
+            self._stepped.append(tab)
 
     def trust_ratios(self):
         """{parameter: its trust ratio r in the last step}, for every parameter that step updated: fresh 0-d device
@@ -759,35 +908,134 @@ class Lamb(_EmaSurface, _HostClip, torch.optim.Optimizer):
     swap_ema = EmaAdamW.swap_ema
 
 
+def _decays(name, p, no_decay):
+    """param_groups_weight_decay's rule: does the parameter `p` called `name` take weight decay?"""
+    listed = name in no_decay or name.rsplit(".", 1)[-1] in no_decay
+    return not (p.ndim <= 1 or name.endswith(".bias") or listed)
+
+
 def param_groups_weight_decay(model, weight_decay, no_decay=("cls_tkn_embd", "pos_embd")):
     """timm's split of a model's trainable parameters into two `param_groups`: `weight_decay = 0` for every parameter
     with `ndim <= 1`, every one whose name ends in ".bias", and every one named in `no_decay` (by its full name or by
     the last component of it, so "pos_embd" names "emdeddings.pos_embd"); `weight_decay` for everything else.
     Parameters with requires_grad off are left out.  LAMB's rule for `weight_decay == 0` tensors (no trust ratio)
     only bites where biases and norm weights sit in such a group; nothing calls this unless asked to."""
-    decay, plain = [], []
+    plain, decay = [], []
     for name, p in model.named_parameters():
-        if not p.requires_grad:
-            continue
-        listed = name in no_decay or name.rsplit(".", 1)[-1] in no_decay
-        (plain if p.ndim <= 1 or name.endswith(".bias") or listed else decay).append(p)
+        if p.requires_grad:
+            (plain, decay)[_decays(name, p, no_decay)].append(p)
     return [{"params": plain, "weight_decay": 0.0}, {"params": decay, "weight_decay": weight_decay}]
 
 
+def _layer_id(name, num_blocks):
+    """timm's layer id on this model's tree: the embeddings 0, encoder block l is l + 1, everything else (the head)
+    num_blocks + 1."""
+    parts = name.split(".")
+    if parts[0] == "emdeddings":
+        return 0
+    if parts[:2] == ["transformer_encoder", "blocks"] and len(parts) > 2 and parts[2].isdigit():
+        return int(parts[2]) + 1
+    return num_blocks + 1
+
+
+def param_groups_layer_decay(model, weight_decay, layer_decay, no_decay=("cls_tkn_embd", "pos_embd")):
+    """timm's layer-wise learning-rate decay (BEiT / MAE / DeiT-III fine-tuning) as `param_groups`: a parameter of
+    layer i of L + 2 (the embeddings are layer 0, `transformer_encoder.blocks.{l}` is l + 1, the `mlp` head L + 1) goes
+    into a group with `lr_scale = layer_decay ** (L + 1 - i)`, so the head trains at the full rate and every layer
+    below it at `layer_decay` times the rate of the one above.  Within a layer param_groups_weight_decay's rule splits
+    decay from no decay; the groups come in ascending layer order, no-decay first, empty ones dropped, parameters
+    with requires_grad off left out.  `lr_scale` takes effect through LRSchedule, which sets
+    `group["lr"] = value * lr_scale` (kind "constant" for a fixed rate)."""
+    if not 0.0 < layer_decay <= 1.0:
+        raise ValueError(f"layer_decay must lie in (0, 1] (got {layer_decay!r})")
+    L = len(model.transformer_encoder.blocks)
+    layers = [([], []) for _ in range(L + 2)]      # per layer: (no decay, decay)
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            layers[_layer_id(name, L)][_decays(name, p, no_decay)].append(p)
+    return [{"params": ps, "weight_decay": wd, "lr_scale": layer_decay ** (L + 1 - i)}
+            for i, pair in enumerate(layers) for ps, wd in zip(pair, (0.0, weight_decay)) if ps]
+
+
+class LRSchedule:
+    """A per-step learning-rate schedule with linear warmup over any torch.optim.Optimizer: timm's CosineLRScheduler
+    with `warmup_prefix=True`, `t_in_epochs=False` and `t_initial = total_steps - warmup_steps` (kind "cosine"), or a
+    constant rate after the same warmup (kind "constant").  Stepped once per optimizer step, not per epoch.  A group's
+    base rate is `group.setdefault("initial_lr", group["lr"])` (torch's convention; it survives load_state_dict).  For
+    the update with 0-based index t, W = warmup_steps, N = total_steps:
+
+        t < W:      v = warmup_lr + (base - warmup_lr) * t / W
+        W <= t < N: v = min_lr + (base - min_lr) * (1 + cos(pi * (t - W) / (N - W))) / 2      (constant: v = base)
+        t >= N:     v = min_lr                                                                (constant: v = base)
+
+    in Python doubles, and `group["lr"] = v * group.get("lr_scale", 1.0)` (param_groups_layer_decay's scale).
+    Constructing it applies t = 0; step() advances t and applies; set_step(t) applies at a given t; state_dict()
+    carries only t.  On the device nothing is copied: FusedAdamW reads `group["lr"]` at every step."""
+
+    KINDS = ("constant", "cosine")
+
+    def __init__(self, optimizer, kind, total_steps, warmup_steps=0, warmup_lr=0.0, min_lr=0.0):
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {self.KINDS} (got {kind!r})")
+        if total_steps < 0 or warmup_steps < 0 or warmup_lr < 0 or min_lr < 0:
+            raise ValueError("total_steps, warmup_steps, warmup_lr and min_lr must not be negative")
+        if warmup_steps > total_steps:
+            raise ValueError(f"warmup_steps ({warmup_steps}) exceeds total_steps ({total_steps})")
+        self.optimizer, self.kind = optimizer, kind
+        self.total_steps, self.warmup_steps = int(total_steps), int(warmup_steps)
+        self.warmup_lr, self.min_lr = float(warmup_lr), float(min_lr)
+        for group in optimizer.param_groups:
+            group.setdefault("initial_lr", group["lr"])
+        self.set_step(0)
+
+    def value(self, base, t):
+        """The rate at update `t` of a group whose base rate is `base`, before its lr_scale."""
+        W, N = self.warmup_steps, self.total_steps
+        if t < W:
+            return self.warmup_lr + (base - self.warmup_lr) * t / W
+        if self.kind == "constant":
+            return base
+        if t >= N:
+            return self.min_lr
+        return self.min_lr + 0.5 * (base - self.min_lr) * (1.0 + math.cos(math.pi * (t - W) / (N - W)))
+
+    def set_step(self, t):
+        self.t = int(t)
+        for group in self.optimizer.param_groups:
+            base = group.setdefault("initial_lr", group["lr"])
+            group["lr"] = self.value(base, self.t) * group.get("lr_scale", 1.0)
+
+    def step(self):
+        self.set_step(self.t + 1)
+
+    def last_lr(self):
+        """The first group's rate before its lr_scale: what train() logs."""
+        group = self.optimizer.param_groups[0]
+        return self.value(group["initial_lr"], self.t)
+
+    def state_dict(self):
+        return {"t": self.t}
+
+    def load_state_dict(self, state_dict):
+        self.set_step(state_dict["t"])
+
+
 def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda", max_grad_norm=None, skip_nonfinite=True,
-                   ema_decay=None, opt="adamw", always_adapt=False, trust_clip=False):
+                   ema_decay=None, opt="adamw", always_adapt=False, trust_clip=False, fuse_groups=False):
     """The reference's optimizer (train.py:66, AdamW(lr, weight_decay=1e-4)): FusedAdamW on a ROCm device,
     torch.optim.AdamW on the host path.  `max_grad_norm` (not in the reference) clips by global gradient norm inside
     the step: FusedAdamW's own keyword on the device, ClippedAdamW on the host.  `ema_decay` (not in the reference
     either) keeps an EMA of the weights inside the step: FusedAdamW's keyword on the device, EmaAdamW on the host.
     `opt="lamb"` (not in the reference) gives FusedLamb on the device and Lamb on the host, with `always_adapt` and
-    `trust_clip` as their group defaults; `params` may be param_groups_weight_decay()'s groups."""
+    `trust_clip` as their group defaults; `params` may be param_groups_weight_decay()'s or
+    param_groups_layer_decay()'s groups.  `fuse_groups` is FusedAdamW's / FusedLamb's keyword: every group in one
+    launch; the host path ignores it."""
     if opt not in ("adamw", "lamb"):
         raise ValueError(f"opt must be 'adamw' or 'lamb' (got {opt!r})")
     if opt == "lamb":
-        cls = Lamb if torch.device(device).type == "cpu" else FusedLamb
+        cls, kw = (Lamb, {}) if torch.device(device).type == "cpu" else (FusedLamb, dict(fuse_groups=fuse_groups))
         return cls(params, lr=lr, weight_decay=weight_decay, always_adapt=always_adapt, trust_clip=trust_clip,
-                   max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+                   max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, **kw)
     if always_adapt or trust_clip:
         raise ValueError("always_adapt and trust_clip belong to opt='lamb'")
     if torch.device(device).type == "cpu":
@@ -797,7 +1045,7 @@ def make_optimizer(params, lr=1e-4, weight_decay=1e-4, device="cuda", max_grad_n
             return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
         return ClippedAdamW(params, max_grad_norm, skip_nonfinite, lr=lr, weight_decay=weight_decay)
     return FusedAdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                      skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+                      skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, fuse_groups=fuse_groups)
 
 
 class CrossEntropyLoss(nn.Module):

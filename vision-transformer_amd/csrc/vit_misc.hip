@@ -717,6 +717,137 @@ __global__ __launch_bounds__(256) void lamb_update_kernel(const vit_tensor_chunk
   else lamb_update_chunk<TS, false>(ch, step, c1, c2, wd);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Grouped steps (vit_hip.h "Grouped optimizer steps"): the kernels above with the launch scalars of up to
+// VIT_OPT_MAX_GROUPS param groups in ONE launch.  The per-group factors, formed on the host exactly as adamw_factors
+// and lamb_factors form them, travel by value in the kernel-argument segment (CsBatch above is the precedent), so a
+// learning rate that changes every step costs no copy.  group_of_chunk[blockIdx.x] is made wave-uniform with
+// readfirstlane before it indexes the struct: the factors then come by scalar loads from the kernel arguments, and
+// the struct is never copied to private memory.  A chunk (or tensor) whose group index is not below `n` returns
+// without touching anything.  The element arithmetic is the device functions above, called as the single-group
+// kernels call them, so every chunk comes out bit for bit as from its group's own launch.
+// ---------------------------------------------------------------------------------------------------------------
+struct AdamwGroup {      // 32 bytes: one 8-dword scalar load
+  float lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, pad;
+};
+struct AdamwGroups {
+  AdamwGroup g[VIT_OPT_MAX_GROUPS];
+  int n;
+};
+struct LambGroup {       // 32 bytes
+  float lr, b1, b2, c1, c2, wd;
+  int adapt, trust_clip;
+};
+struct LambGroups {
+  LambGroup g[VIT_OPT_MAX_GROUPS];
+  int n;
+};
+
+// adamw_kernel / adamw_clipped_kernel / adamw_ema_kernel in one: clip and ema may each be NULL.
+template <class TS>
+__global__ __launch_bounds__(256) void adamw_groups_kernel(const vit_tensor_chunk* __restrict__ tab,
+                                                           float* const* __restrict__ ema,
+                                                           const int32_t* __restrict__ group_of_chunk,
+                                                           const AdamwGroups gs, float gscale, float ema_w,
+                                                           const float* __restrict__ clip) {
+  if (clip) {
+    if (clip[2] != 0.f) return;
+    gscale = gscale * clip[1];
+  }
+  const unsigned gi = (unsigned)__builtin_amdgcn_readfirstlane(group_of_chunk[blockIdx.x]);
+  if (gi >= (unsigned)gs.n) return;
+  const AdamwGroup& h = gs.g[gi];
+  const vit_tensor_chunk ch = tab[blockIdx.x];
+  float* const ema_p = ema ? ema[blockIdx.x] : nullptr;
+  if (!ema_p) {
+    adamw_chunk<TS>(ch, h.lr, h.b1, h.b2, h.eps, h.wd, h.step_size, h.inv_sqrt_bc2, gscale);
+    return;
+  }
+  adamw_chunk<TS, true>(ch, h.lr, h.b1, h.b2, h.eps, h.wd, h.step_size, h.inv_sqrt_bc2, gscale, ema_p, ema_w);
+}
+
+// lamb_moments_kernel's body with the group's factors.
+__global__ __launch_bounds__(256) void lamb_moments_groups_kernel(const vit_tensor_chunk* __restrict__ tab,
+                                                                  const int32_t* __restrict__ group_of_chunk,
+                                                                  const LambGroups gs, float gscale,
+                                                                  const float* __restrict__ clip,
+                                                                  double* __restrict__ partial) {
+  __shared__ double red_p[4], red_u[4];
+  if (clip) {
+    if (clip[2] != 0.f) return;
+    gscale = gscale * clip[1];
+  }
+  const unsigned gi = (unsigned)__builtin_amdgcn_readfirstlane(group_of_chunk[blockIdx.x]);
+  if (gi >= (unsigned)gs.n) return;
+  const LambGroup& h = gs.g[gi];
+  const float b1 = h.b1, b2 = h.b2, c1 = h.c1, c2 = h.c2, wd = h.wd;
+  const vit_tensor_chunk ch = tab[blockIdx.x];
+  double sp = 0.0, su = 0.0;
+  for (int64_t t = threadIdx.x; t < ch.n; t += 256) {
+    const float g = ch.g[t] * gscale;
+    float m = ch.m[t], v = ch.v[t];
+    const float p = ch.p[t];
+    m = __builtin_fmaf(b1, m, (1.0f - b1) * g);
+    v = __builtin_fmaf(b2, v, (1.0f - b2) * g * g);
+    const float u = lamb_u(m, v, p, c1, c2, wd);
+    ch.m[t] = m;
+    ch.v[t] = v;
+    sp += (double)p * (double)p;
+    su += (double)u * (double)u;
+  }
+  sp = block_sum_f64(sp, red_p);
+  su = block_sum_f64(su, red_u);
+  if (threadIdx.x == 0) {
+    partial[2 * (int64_t)blockIdx.x] = sp;
+    partial[2 * (int64_t)blockIdx.x + 1] = su;
+  }
+}
+
+// lamb_trust_kernel's body with the flags of the tensor's group.
+__global__ __launch_bounds__(256) void lamb_trust_groups_kernel(const double* __restrict__ partial,
+                                                                const int32_t* __restrict__ first,
+                                                                const int32_t* __restrict__ group_of_tensor,
+                                                                const LambGroups gs, float* __restrict__ trust,
+                                                                const float* __restrict__ clip) {
+  __shared__ double red_p[4], red_u[4];
+  if (clip && clip[2] != 0.f) return;
+  const unsigned gi = (unsigned)__builtin_amdgcn_readfirstlane(group_of_tensor[blockIdx.x]);
+  if (gi >= (unsigned)gs.n) return;
+  const int adapt = gs.g[gi].adapt, trust_clip = gs.g[gi].trust_clip;
+  const int64_t lo = first[blockIdx.x], hi = first[blockIdx.x + 1];
+  double sp = 0.0, su = 0.0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+    sp += partial[2 * i];
+    su += partial[2 * i + 1];
+  }
+  sp = block_sum_f64(sp, red_p);
+  su = block_sum_f64(su, red_u);
+  if (threadIdx.x != 0) return;
+  float r = 1.f;
+  if (adapt && sp > 0.0 && su > 0.0) r = (float)(sqrt(sp) / sqrt(su));
+  if (trust_clip && r > 1.f) r = 1.f;
+  trust[blockIdx.x] = r;
+}
+
+template <class TS>
+__global__ __launch_bounds__(256) void lamb_update_groups_kernel(const vit_tensor_chunk* __restrict__ tab,
+                                                                 float* const* __restrict__ ema,
+                                                                 const int32_t* __restrict__ tensor_of_chunk,
+                                                                 const float* __restrict__ trust,
+                                                                 const int32_t* __restrict__ group_of_chunk,
+                                                                 const LambGroups gs, float ema_w,
+                                                                 const float* __restrict__ clip) {
+  if (clip && clip[2] != 0.f) return;
+  const unsigned gi = (unsigned)__builtin_amdgcn_readfirstlane(group_of_chunk[blockIdx.x]);
+  if (gi >= (unsigned)gs.n) return;
+  const LambGroup& h = gs.g[gi];
+  const vit_tensor_chunk ch = tab[blockIdx.x];
+  const float step = h.lr * trust[tensor_of_chunk[blockIdx.x]];
+  float* const ema_p = ema ? ema[blockIdx.x] : nullptr;
+  if (ema_p) lamb_update_chunk<TS, true>(ch, step, h.c1, h.c2, h.wd, ema_p, ema_w);
+  else lamb_update_chunk<TS, false>(ch, step, h.c1, h.c2, h.wd);
+}
+
 }  // namespace
 
 // ===============================================================================================================
@@ -1088,5 +1219,111 @@ extern "C" int vit_pack(const vit_tensor_chunk* table_dev, int64_t nchunks, int3
   VIT_REQUIRE(table_dev && nchunks > 0, "vit_pack: bad arguments");
   TABLE_LAUNCH(pack_kernel, table_dev);
   return vit::check_launch("vit_pack");
+}
+
+// What the four grouped entry points check alike, under the name `who` of the one that was called (`lamb`: the LAMB
+// flags are allowed).  `count` is nchunks, or ntensors for the trust pass.
+static int check_opt_groups(const char* who, bool ptrs, int64_t count, const vit_opt_group* groups, int32_t ngroups,
+                            bool lamb) {
+  VIT_REQUIRE(ptrs && groups, "%s: null pointer", who);
+  VIT_REQUIRE(count > 0 && count <= 0x3fffffff, "%s: the chunk / tensor count must be positive (got %lld)", who,
+              (long long)count);
+  VIT_REQUIRE(ngroups >= 1 && ngroups <= VIT_OPT_MAX_GROUPS, "%s: ngroups must lie in 1..%d (got %d)", who,
+              VIT_OPT_MAX_GROUPS, (int)ngroups);
+  for (int32_t i = 0; i < ngroups; ++i) {
+    const vit_opt_group& g = groups[i];
+    VIT_REQUIRE(g.bias_corr1 > 0.f && g.bias_corr1 <= 1.f && g.bias_corr2 > 0.f && g.bias_corr2 <= 1.f,
+                "%s: group %d: bias corrections must lie in (0, 1] (got %g, %g)", who, (int)i, (double)g.bias_corr1,
+                (double)g.bias_corr2);
+    VIT_REQUIRE(g.eps >= 0.f, "%s: group %d: eps must not be negative (got %g)", who, (int)i, (double)g.eps);
+    VIT_REQUIRE(fabsf(g.lr) <= 3.402823466e+38f, "%s: group %d: lr must be finite (got %g)", who, (int)i,
+                (double)g.lr);
+    if (lamb)
+      VIT_REQUIRE((g.flags & ~(VIT_OPT_ADAPT | VIT_OPT_TRUST_CLIP)) == 0, "%s: group %d: unknown flags 0x%x", who,
+                  (int)i, (unsigned)g.flags);
+    else
+      VIT_REQUIRE(g.flags == 0, "%s: group %d: flags must be 0 for AdamW (got 0x%x)", who, (int)i,
+                  (unsigned)g.flags);
+  }
+  return VIT_OK;
+}
+
+// The kernel-argument struct of the LAMB passes: lamb_factors' c1 and c2 per group.
+static int lamb_group_args(const char* who, bool ptrs, int64_t count, const vit_opt_group* groups, int32_t ngroups,
+                           LambGroups* out) {
+  if (int rc = check_opt_groups(who, ptrs, count, groups, ngroups, true)) return rc;
+  memset(out, 0, sizeof(*out));
+  out->n = ngroups;
+  for (int32_t i = 0; i < ngroups; ++i) {
+    const vit_opt_group& g = groups[i];
+    LambGroup& h = out->g[i];
+    h.lr = g.lr, h.b1 = g.beta1, h.b2 = g.beta2, h.wd = g.weight_decay;
+    h.c1 = (float)((double)g.bias_corr1 / sqrt((double)g.bias_corr2));
+    h.c2 = (float)((double)g.bias_corr1 * (double)g.eps);
+    h.adapt = (g.flags & VIT_OPT_ADAPT) != 0, h.trust_clip = (g.flags & VIT_OPT_TRUST_CLIP) != 0;
+  }
+  return VIT_OK;
+}
+
+extern "C" int vit_adamw_groups(const vit_tensor_chunk* table_dev, float* const* ema_dev,
+                                const int32_t* group_of_chunk, int64_t nchunks, const vit_opt_group* groups,
+                                int32_t ngroups, float grad_scale, int32_t shadow_dtype, float ema_weight,
+                                const float* clip, void* stream) {
+  if (int rc = check_opt_groups("vit_adamw_groups", table_dev && group_of_chunk, nchunks, groups, ngroups, false))
+    return rc;
+  VIT_REQUIRE(!ema_dev || (ema_weight > 0.f && ema_weight < 1.f),
+              "vit_adamw_groups: ema_weight must lie in (0, 1) (got %g)", (double)ema_weight);
+  AdamwGroups gs;
+  memset(&gs, 0, sizeof(gs));
+  gs.n = ngroups;
+  for (int32_t i = 0; i < ngroups; ++i) {
+    const vit_opt_group& g = groups[i];
+    AdamwGroup& h = gs.g[i];
+    h.lr = g.lr, h.b1 = g.beta1, h.b2 = g.beta2, h.eps = g.eps, h.wd = g.weight_decay;
+    h.step_size = g.lr / g.bias_corr1;                  // adamw_factors' two, the same floats
+    h.inv_sqrt_bc2 = 1.0f / sqrtf(g.bias_corr2);
+  }
+  TABLE_LAUNCH(adamw_groups_kernel, table_dev, ema_dev, group_of_chunk, gs, grad_scale, ema_weight, clip);
+  return vit::check_launch("vit_adamw_groups");
+}
+
+extern "C" int vit_lamb_moments_groups(const vit_tensor_chunk* table_dev, const int32_t* group_of_chunk,
+                                       int64_t nchunks, const vit_opt_group* groups, int32_t ngroups,
+                                       float grad_scale, const float* clip, double* partial, void* stream) {
+  LambGroups gs;
+  if (int rc = lamb_group_args("vit_lamb_moments_groups", table_dev && group_of_chunk && partial, nchunks, groups,
+                               ngroups, &gs))
+    return rc;
+  lamb_moments_groups_kernel<<<(unsigned)nchunks, 256, 0, VIT_STREAM(stream)>>>(table_dev, group_of_chunk, gs,
+                                                                                grad_scale, clip, partial);
+  return vit::check_launch("vit_lamb_moments_groups");
+}
+
+extern "C" int vit_lamb_trust_groups(const double* partial, const int32_t* tensor_first,
+                                     const int32_t* group_of_tensor, int64_t ntensors, const vit_opt_group* groups,
+                                     int32_t ngroups, float* trust, const float* clip, void* stream) {
+  LambGroups gs;
+  if (int rc = lamb_group_args("vit_lamb_trust_groups", partial && tensor_first && group_of_tensor && trust, ntensors,
+                               groups, ngroups, &gs))
+    return rc;
+  lamb_trust_groups_kernel<<<(unsigned)ntensors, 256, 0, VIT_STREAM(stream)>>>(partial, tensor_first, group_of_tensor,
+                                                                               gs, trust, clip);
+  return vit::check_launch("vit_lamb_trust_groups");
+}
+
+extern "C" int vit_lamb_update_groups(const vit_tensor_chunk* table_dev, float* const* ema_dev,
+                                      const int32_t* tensor_of_chunk, const float* trust,
+                                      const int32_t* group_of_chunk, int64_t nchunks, const vit_opt_group* groups,
+                                      int32_t ngroups, int32_t shadow_dtype, float ema_weight, const float* clip,
+                                      void* stream) {
+  LambGroups gs;
+  if (int rc = lamb_group_args("vit_lamb_update_groups", table_dev && tensor_of_chunk && trust && group_of_chunk,
+                               nchunks, groups, ngroups, &gs))
+    return rc;
+  VIT_REQUIRE(!ema_dev || (ema_weight > 0.f && ema_weight < 1.f),
+              "vit_lamb_update_groups: ema_weight must lie in (0, 1) (got %g)", (double)ema_weight);
+  TABLE_LAUNCH(lamb_update_groups_kernel, table_dev, ema_dev, tensor_of_chunk, trust, group_of_chunk, gs, ema_weight,
+               clip);
+  return vit::check_launch("vit_lamb_update_groups");
 }
 #undef TABLE_LAUNCH

@@ -31,7 +31,8 @@ import torch
 import torch.distributed as dist
 
 from VisionTransformer import config, vit
-from VisionTransformer.optim import MixedLabels, cross_entropy, make_optimizer, param_groups_weight_decay
+from VisionTransformer.optim import (LRSchedule, MixedLabels, cross_entropy, make_optimizer, param_groups_layer_decay,
+                                     param_groups_weight_decay)
 
 device = "cuda" if torch.cuda.is_available() else "cpu"
 
@@ -192,17 +193,36 @@ def _rank_world():
     return 0, 1
 
 
-def _optimizer(model, lr, dev, opt="adamw", weight_decay=1e-4, no_decay_1d=False, **kw):
-    """make_optimizer over the model's parameters: one group as the reference has it, or with `no_decay_1d`
-    param_groups_weight_decay's two."""
-    params = param_groups_weight_decay(model, weight_decay) if no_decay_1d else model.parameters()
+def _optimizer(model, lr, dev, opt="adamw", weight_decay=1e-4, no_decay_1d=False, layer_decay=None,
+               fuse_groups=False, **kw):
+    """make_optimizer over the model's parameters: one group as the reference has it, with `no_decay_1d`
+    param_groups_weight_decay's two, or with `layer_decay` param_groups_layer_decay's (timm's: `no_decay_1d`'s split
+    inside every layer), stepped in one launch."""
+    if layer_decay is not None:
+        params = param_groups_layer_decay(model, weight_decay, layer_decay)
+        fuse_groups = True
+    else:
+        params = param_groups_weight_decay(model, weight_decay) if no_decay_1d else model.parameters()
+    if fuse_groups:
+        kw["fuse_groups"] = True
     return make_optimizer(params, lr=lr, weight_decay=weight_decay, device=dev, opt=opt, **kw)
+
+
+def _schedule(optimizer, sched, layer_decay, total_steps, warmup_steps, warmup_lr, min_lr):
+    """The LRSchedule the flags ask for, or None: `sched` names it, and layer decay without one takes a constant
+    schedule, through which param_groups_layer_decay's `lr_scale` reaches `group["lr"]`."""
+    if sched is None and layer_decay is None:
+        if warmup_steps or warmup_lr or min_lr:
+            raise ValueError("warmup_steps, warmup_lr and min_lr belong to a schedule (sched='constant' or 'cosine')")
+        return None
+    return LRSchedule(optimizer, sched or "constant", total_steps, warmup_steps, warmup_lr, min_lr)
 
 
 def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkpoint_dir, lr=1e-4,
           log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None, ema_decay=None,
           label_smoothing=0.0, mix=None, opt="adamw", weight_decay=1e-4, no_decay_1d=False, always_adapt=False,
-          trust_clip=False):
+          trust_clip=False, sched=None, warmup_steps=0, warmup_lr=0.0, min_lr=0.0, layer_decay=None,
+          fuse_groups=False):
     """The reference training loop (train.py:60-119) on the HIP path.  Returns the last epoch's summed loss.
 
     Defaults keep the GPU busy: no host sync inside the epoch — the epoch loss is summed on the device and the per-step
@@ -235,14 +255,29 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     `opt`, `weight_decay`, `no_decay_1d`, `always_adapt`, `trust_clip` (not in the reference, which trains with
     AdamW(weight_decay=1e-4) over one group, train.py:66): `opt="lamb"` steps with LAMB (optim.FusedLamb; Lamb on the
     host path), `no_decay_1d` puts biases, norm weights and the two embeddings into a `weight_decay = 0` group
-    (optim.param_groups_weight_decay), and the two flags are LAMB's.  The checkpoint dict is the same either way."""
+    (optim.param_groups_weight_decay), and the two flags are LAMB's.  The checkpoint dict is the same either way.
+
+    `sched`, `warmup_steps`, `warmup_lr`, `min_lr` (not in the reference, which trains at one constant rate): an
+    optim.LRSchedule ("constant" or "cosine", linear warmup first) over `lr`, stepped after every optimizer step;
+    its length is the number of optimizer steps the run takes, (epochs + 1) epochs of min(len(train_loader),
+    max_steps) steps.  "LR/train_batch", the rate each step was taken at (the first group's, before its `lr_scale`;
+    a host value, no sync), is logged at the loss's cadence, and the checkpoint dict gains one key, "lr_schedule",
+    restored on resume.  `layer_decay`: optim.param_groups_layer_decay's groups, stepped in one launch (`fuse_groups`),
+    under a constant schedule unless one is named.  `fuse_groups` alone steps whatever groups there are in one launch.
+    With none of these the optimizer, its groups, its launches and the checkpoint dict are the reference's."""
     rank, world = _rank_world()
     saved_epoch = search_checkpoint(checkpoint_dir)
     torch.manual_seed(0)                              # identical init on every rank
     model = vit.VisionTransformer(configs)
     opt_kw = dict(opt=opt, weight_decay=weight_decay, no_decay_1d=no_decay_1d, always_adapt=always_adapt,
-                  trust_clip=trust_clip, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+                  trust_clip=trust_clip, max_grad_norm=max_grad_norm, ema_decay=ema_decay, layer_decay=layer_decay,
+                  fuse_groups=fuse_groups)
     optimizer = _optimizer(model, lr, device, **opt_kw)
+    total_steps = 0
+    if sched is not None or layer_decay is not None:      # the optimizer steps of a run from scratch: epochs 0 .. `epochs`
+        total_steps = (epochs + 1) * (min(len(train_loader), max_steps) if max_steps else len(train_loader))
+    sched_args = (sched, layer_decay, total_steps, warmup_steps, warmup_lr, min_lr)
+    schedule = _schedule(optimizer, *sched_args)
     iteration = 0
     if saved_epoch is not None:
         print(f"Checkpoint Found. Loading model from epoch {saved_epoch}")
@@ -251,6 +286,9 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
         model = model.to(device)
         optimizer = _optimizer(model, lr, device, **opt_kw)
         optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        schedule = _schedule(optimizer, *sched_args)
+        if schedule is not None and "lr_schedule" in ckpt:
+            schedule.load_state_dict(ckpt["lr_schedule"])
         iteration = 0 if reference_loop else int(ckpt.get("step", 0))
     else:
         saved_epoch = 0
@@ -287,6 +325,10 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
             optimizer.zero_grad(set_to_none=True)
             loss.backward()
             optimizer.step()
+            if schedule is not None:
+                if writer is not None and (reference_loop or (log_every and iteration % log_every == 0)):
+                    writer.add_scalar("LR/train_batch", schedule.last_lr(), iteration)
+                schedule.step()
             if reference_loop:
                 host_loss += loss.item()
                 if writer is not None:
@@ -324,6 +366,8 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
                     "optimizer_state_dict": optimizer.state_dict(), "loss": running_loss, "step": iteration}
             if ema_decay is not None:
                 ckpt["ema_state_dict"] = optimizer.ema_state_dict(model)
+            if schedule is not None:
+                ckpt["lr_schedule"] = schedule.state_dict()
             torch.save(ckpt, os.path.join(checkpoint_dir, f"{epoch}.pt"))
             ips = nb * configs.batch_size * world / max(dt, 1e-9)
             print(f"Epoch {epoch}, curr loss: {running_loss:.4f}, mean_accuracy: {acc}, "
@@ -338,18 +382,21 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
 
 def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None, ema_decay=None,
                label_smoothing=0.0, mix=None, opt="adamw", weight_decay=1e-4, no_decay_1d=False, always_adapt=False,
-               trust_clip=False):
+               trust_clip=False, layer_decay=None, fuse_groups=False):
     """The hot loop body (train.py:91-98: forward, CE loss, zero_grad(set_to_none), backward, AdamW step) on one
     synthetic batch already resident on `dev`, dropout on; returns (seconds per timed step, last loss).  This is the
     repo's own CPU training step that bench.py's `cpu_baseline` times (BASELINE config 1).  Unclipped unless
     `max_grad_norm` is given, and without a weight EMA unless `ema_decay` is.  With `mix` (a data.BatchMix) every step
     first mixes the resident batch, and `label_smoothing` goes to the loss, as in train().  `opt`, `weight_decay`,
-    `no_decay_1d`, `always_adapt` and `trust_clip` choose the optimizer as in train()."""
+    `no_decay_1d`, `always_adapt`, `trust_clip`, `layer_decay` and `fuse_groups` choose the optimizer as in train()
+    (with `layer_decay` under a constant schedule, applied once: the rates do not move while timing)."""
     dev = torch.device(dev or device)
     torch.manual_seed(0)
     model = vit.VisionTransformer(configs).to(dev).train()
     opt = _optimizer(model, lr, dev, opt=opt, weight_decay=weight_decay, no_decay_1d=no_decay_1d,
-                     always_adapt=always_adapt, trust_clip=trust_clip, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+                     always_adapt=always_adapt, trust_clip=trust_clip, max_grad_norm=max_grad_norm, ema_decay=ema_decay,
+                     layer_decay=layer_decay, fuse_groups=fuse_groups)
+    _schedule(opt, None, layer_decay, 0, 0, 0.0, 0.0)
     g = torch.Generator().manual_seed(seed)
     n_img = int(round((configs.num_patches ** 0.5) * configs.patch_size))
     x = torch.randn(configs.batch_size, configs.input_channels, n_img, n_img, generator=g).to(dev)
@@ -400,6 +447,17 @@ def main():
     ap.add_argument("--lamb-always-adapt", action="store_true",
                     help="LAMB: apply the trust ratio to tensors without weight decay too")
     ap.add_argument("--lamb-trust-clip", action="store_true", help="LAMB: bound every trust ratio by 1")
+    ap.add_argument("--sched", default=None, choices=["constant", "cosine"],
+                    help="per-step learning-rate schedule over --lr, after a linear warmup (default: none, one "
+                         "constant rate as the reference)")
+    ap.add_argument("--warmup-steps", type=int, default=0, metavar="N", help="with --sched: optimizer steps of warmup")
+    ap.add_argument("--warmup-lr", type=float, default=0.0, metavar="F", help="with --sched: the rate the warmup starts at")
+    ap.add_argument("--min-lr", type=float, default=0.0, metavar="F", help="with --sched cosine: the rate it ends at")
+    ap.add_argument("--layer-decay", type=float, default=None, metavar="F",
+                    help="layer-wise learning-rate decay: the head at --lr, every layer below at F times the rate of "
+                         "the one above (timm's rule; turns --fuse-groups on; default: none)")
+    ap.add_argument("--fuse-groups", action="store_true",
+                    help="step every param group in one launch instead of one launch per group")
     ap.add_argument("--drop-path", type=float, default=0.0, metavar="RATE",
                     help="stochastic depth: drop each residual branch per image, block l of L at rate RATE * l / (L - 1) "
                          "(timm's linear rule; DeiT-B trains with 0.1; default 0: off, as the reference)")
@@ -481,7 +539,10 @@ def main():
     if args.opt != "lamb" and (args.lamb_always_adapt or args.lamb_trust_clip):
         ap.error("--lamb-always-adapt and --lamb-trust-clip need --opt lamb")
     opt_args = dict(opt=args.opt, weight_decay=args.weight_decay, no_decay_1d=args.no_decay_1d,
-                    always_adapt=args.lamb_always_adapt, trust_clip=args.lamb_trust_clip)
+                    always_adapt=args.lamb_always_adapt, trust_clip=args.lamb_trust_clip, layer_decay=args.layer_decay,
+                    fuse_groups=args.fuse_groups)
+    if args.sched is None and args.layer_decay is None and (args.warmup_steps or args.warmup_lr or args.min_lr):
+        ap.error("--warmup-steps, --warmup-lr and --min-lr need --sched")
     if args.bench:
         steps = args.steps or 30
         sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm,
@@ -533,7 +594,8 @@ def main():
                                                   sampler=tsampler, drop_last=False, pin_memory=pin)
     train(cfg, train_loader, test_loader, args.epochs, args.eval_iter, args.log_dir, args.checkpoint_dir,
           lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop, max_grad_norm=args.clip_grad_norm,
-          ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix, **opt_args)
+          ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix, sched=args.sched,
+          warmup_steps=args.warmup_steps, warmup_lr=args.warmup_lr, min_lr=args.min_lr, **opt_args)
     if world > 1:
         dist.destroy_process_group()
 
