@@ -547,15 +547,23 @@ def adamw(table_dev, nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, b
         _lib.call("vit_adamw", _ptr(table_dev), nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2,
                   grad_scale, dtype_code(shadow_dtype), _stream(stream))
         return
-    _check_clip(clip)
     _lib.call("vit_adamw_clipped", _ptr(table_dev), nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1,
-              bias_corr2, grad_scale, dtype_code(shadow_dtype), _ptr(clip), _stream(stream))
+              bias_corr2, grad_scale, dtype_code(shadow_dtype), _clip_ptr(clip), _stream(stream))
 
 
 def _check_clip(clip):
     _need_cuda(clip)
     if clip.dtype != torch.float32 or clip.numel() < 4 or not clip.is_contiguous():
         raise ValueError("clip state must be a contiguous float32 tensor of at least 4 elements")
+
+
+def _clip_ptr(clip):
+    """The pointer of a step's clip block, checked; None (NULL) for the unclipped step.  No deeper in calls than the
+    checks it replaces, nor is _ema_args: they run for every launch of a per-group step, whose pace the host sets."""
+    if clip is None:
+        return None
+    _check_clip(clip)
+    return ctypes.c_void_p(clip.data_ptr())
 
 
 def grad_sumsq(table_dev, nchunks, grad_scale, partial, stream=None):
@@ -636,16 +644,22 @@ def _check_ema(ema_dev, nchunks):
         raise ValueError(f"the EMA pointer array must be a contiguous int64 tensor of {nchunks} elements")
 
 
+def _ema_args(ema_dev, ema_decay, nchunks, optional=True):
+    """(pointer, weight) of a step's EMA; (NULL, 0) for an `optional` one that is not kept.  The weight 1 - ema_decay
+    is formed in double here and rounded to fp32 once, as the `float` argument it becomes."""
+    if ema_dev is None and optional:
+        return None, 0.0
+    _check_ema(ema_dev, nchunks)
+    return ctypes.c_void_p(ema_dev.data_ptr()), 1.0 - float(ema_decay)
+
+
 def adamw_ema(table_dev, ema_dev, nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale,
               shadow_dtype, ema_decay, stream=None, clip=None):
     """vit_adamw_ema: the (clipped, with `clip`) AdamW update, then e += (1 - ema_decay) * (p_new - e) for every chunk
-    whose EMA pointer is set.  The weight 1 - ema_decay is formed in double here and rounded to fp32 once."""
-    _check_ema(ema_dev, nchunks)
-    if clip is not None:
-        _check_clip(clip)
-    _lib.call("vit_adamw_ema", _ptr(table_dev), _ptr(ema_dev), nchunks, lr, beta1, beta2, eps, weight_decay,
-              bias_corr1, bias_corr2, grad_scale, dtype_code(shadow_dtype), 1.0 - float(ema_decay),
-              _ptr(clip), _stream(stream))
+    whose EMA pointer is set."""
+    ema_p, ema_w = _ema_args(ema_dev, ema_decay, nchunks, optional=False)
+    _lib.call("vit_adamw_ema", _ptr(table_dev), ema_p, nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1,
+              bias_corr2, grad_scale, dtype_code(shadow_dtype), ema_w, _clip_ptr(clip), _stream(stream))
 
 
 def ema_swap(table_dev, ema_dev, nchunks, shadow_dtype, stream=None):
@@ -671,10 +685,22 @@ def build_tensor_index(entries, device):
             len(entries), len(owner))
 
 
-def _check_lamb_buffer(t, dtype, numel, what):
+def _check_lamb_buffer(t, dtype, numel, what, exactly=None):
+    """A contiguous device tensor of `dtype` with at least `numel` elements; with `exactly` (how the message names
+    that count: "nchunks = ", or "" for the number alone) no more than that either, as an index array has."""
     _need_cuda(t)
     if t is None or t.dtype != dtype or t.numel() < numel or not t.is_contiguous():
         raise ValueError(f"{what} must be a contiguous {dtype} device tensor of at least {numel} elements")
+    if exactly is not None and t.numel() != numel:
+        raise ValueError(f"{what} must have {exactly}{numel} elements")
+
+
+def _check_partial_sums(partial):
+    """The partials the trust pass reads, indexed by the tensor index: any length."""
+    if partial is None or partial.dtype != torch.float64 or not partial.is_contiguous():
+        raise ValueError("partial must be a contiguous float64 device tensor")
+    if not partial.is_cuda:
+        _need_cuda(partial)      # raises, with its message
 
 
 def lamb_moments(table_dev, nchunks, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale, partial,
@@ -683,26 +709,18 @@ def lamb_moments(table_dev, nchunks, beta1, beta2, eps, weight_decay, bias_corr1
     u^2.  `partial`: float64 device tensor of at least 2 * nchunks elements.  `clip` as in adamw()."""
     _need_cuda(table_dev)
     _check_lamb_buffer(partial, torch.float64, 2 * nchunks, "partial")
-    if clip is not None:
-        _check_clip(clip)
     _lib.call("vit_lamb_moments", _ptr(table_dev), nchunks, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2,
-              grad_scale, _ptr(clip), _ptr(partial), _stream(stream))
+              grad_scale, _clip_ptr(clip), _ptr(partial), _stream(stream))
 
 
 def lamb_trust(partial, tensor_first, ntensors, trust, adapt=True, trust_clip=False, stream=None, clip=None):
     """vit_lamb_trust: trust[i] = |p| / |u| of tensor i from lamb_moments' partials where `adapt` is set and both norms
     are positive, else 1; at most 1 with `trust_clip`.  `tensor_first` from build_tensor_index."""
-    _check_lamb_buffer(tensor_first, torch.int32, ntensors + 1, "tensor_first")
-    if tensor_first.numel() != ntensors + 1:
-        raise ValueError(f"tensor_first must have ntensors + 1 = {ntensors + 1} elements")
+    _check_lamb_buffer(tensor_first, torch.int32, ntensors + 1, "tensor_first", "ntensors + 1 = ")
     _check_lamb_buffer(trust, torch.float32, ntensors, "trust")
-    if partial is None or partial.dtype != torch.float64 or not partial.is_contiguous():
-        raise ValueError("partial must be a contiguous float64 device tensor")
-    _need_cuda(partial)
-    if clip is not None:
-        _check_clip(clip)
+    _check_partial_sums(partial)
     _lib.call("vit_lamb_trust", _ptr(partial), _ptr(tensor_first), ntensors, int(bool(adapt)), int(bool(trust_clip)),
-              _ptr(trust), _ptr(clip), _stream(stream))
+              _ptr(trust), _clip_ptr(clip), _stream(stream))
 
 
 def lamb_update(table_dev, tensor_of_chunk, trust, nchunks, lr, eps, weight_decay, bias_corr1, bias_corr2,
@@ -711,18 +729,11 @@ def lamb_update(table_dev, tensor_of_chunk, trust, nchunks, lr, eps, weight_deca
     EMA of adamw_ema() for every chunk whose pointer is set.  eps, weight_decay and the bias corrections are those
     lamb_moments was given."""
     _need_cuda(table_dev)
-    _check_lamb_buffer(tensor_of_chunk, torch.int32, nchunks, "tensor_of_chunk")
-    if tensor_of_chunk.numel() != nchunks:
-        raise ValueError(f"tensor_of_chunk must have nchunks = {nchunks} elements")
+    _check_lamb_buffer(tensor_of_chunk, torch.int32, nchunks, "tensor_of_chunk", "nchunks = ")
     _check_lamb_buffer(trust, torch.float32, 1, "trust")
-    ema_w = 0.0
-    if ema_dev is not None:
-        _check_ema(ema_dev, nchunks)
-        ema_w = 1.0 - float(ema_decay)
-    if clip is not None:
-        _check_clip(clip)
-    _lib.call("vit_lamb_update", _ptr(table_dev), _ptr(ema_dev), _ptr(tensor_of_chunk), _ptr(trust), nchunks, lr, eps,
-              weight_decay, bias_corr1, bias_corr2, dtype_code(shadow_dtype), ema_w, _ptr(clip), _stream(stream))
+    ema_p, ema_w = _ema_args(ema_dev, ema_decay, nchunks)
+    _lib.call("vit_lamb_update", _ptr(table_dev), ema_p, _ptr(tensor_of_chunk), _ptr(trust), nchunks, lr, eps,
+              weight_decay, bias_corr1, bias_corr2, dtype_code(shadow_dtype), ema_w, _clip_ptr(clip), _stream(stream))
 
 
 # ---- grouped steps (vit_hip.h "Grouped optimizer steps") -----------------------------------------------------------
@@ -754,56 +765,37 @@ def opt_groups(specs):
     return (_lib.OptGroup * len(specs)).from_buffer_copy(packed)
 
 
-def _check_group_index(t, numel, what):
-    _check_lamb_buffer(t, torch.int32, numel, what)
-    if t.numel() != numel:
-        raise ValueError(f"{what} must have {numel} elements")
-
-
 def adamw_groups(table_dev, group_of_chunk, nchunks, specs, grad_scale, shadow_dtype, ema_dev=None, ema_decay=None,
                  stream=None, clip=None):
     """vit_adamw_groups: adamw() / adamw_ema() over the chunks of several groups in one launch; chunk i takes the
     scalars of specs[group_of_chunk[i]] (opt_groups).  `ema_dev` / `ema_decay` and `clip` as in adamw_ema()."""
     _need_cuda(table_dev)
-    _check_group_index(group_of_chunk, nchunks, "group_of_chunk")
-    ema_w = 0.0
-    if ema_dev is not None:
-        _check_ema(ema_dev, nchunks)
-        ema_w = 1.0 - float(ema_decay)
-    if clip is not None:
-        _check_clip(clip)
-    groups = opt_groups(specs)
-    _lib.call("vit_adamw_groups", _ptr(table_dev), _ptr(ema_dev), _ptr(group_of_chunk), nchunks, groups, len(groups),
-              grad_scale, dtype_code(shadow_dtype), ema_w, _ptr(clip), _stream(stream))
+    _check_lamb_buffer(group_of_chunk, torch.int32, nchunks, "group_of_chunk", "")
+    ema_p, ema_w = _ema_args(ema_dev, ema_decay, nchunks)
+    clip_p, groups = _clip_ptr(clip), opt_groups(specs)
+    _lib.call("vit_adamw_groups", _ptr(table_dev), ema_p, _ptr(group_of_chunk), nchunks, groups, len(groups),
+              grad_scale, dtype_code(shadow_dtype), ema_w, clip_p, _stream(stream))
 
 
 def lamb_moments_groups(table_dev, group_of_chunk, nchunks, specs, grad_scale, partial, stream=None, clip=None):
     """vit_lamb_moments_groups: lamb_moments() with each chunk's scalars from specs[group_of_chunk[i]]."""
     _need_cuda(table_dev)
-    _check_group_index(group_of_chunk, nchunks, "group_of_chunk")
+    _check_lamb_buffer(group_of_chunk, torch.int32, nchunks, "group_of_chunk", "")
     _check_lamb_buffer(partial, torch.float64, 2 * nchunks, "partial")
-    if clip is not None:
-        _check_clip(clip)
-    groups = opt_groups(specs)
+    clip_p, groups = _clip_ptr(clip), opt_groups(specs)
     _lib.call("vit_lamb_moments_groups", _ptr(table_dev), _ptr(group_of_chunk), nchunks, groups, len(groups),
-              grad_scale, _ptr(clip), _ptr(partial), _stream(stream))
+              grad_scale, clip_p, _ptr(partial), _stream(stream))
 
 
 def lamb_trust_groups(partial, tensor_first, group_of_tensor, ntensors, specs, trust, stream=None, clip=None):
     """vit_lamb_trust_groups: lamb_trust() with each tensor's flags from specs[group_of_tensor[i]]."""
-    _check_lamb_buffer(tensor_first, torch.int32, ntensors + 1, "tensor_first")
-    if tensor_first.numel() != ntensors + 1:
-        raise ValueError(f"tensor_first must have ntensors + 1 = {ntensors + 1} elements")
-    _check_group_index(group_of_tensor, ntensors, "group_of_tensor")
+    _check_lamb_buffer(tensor_first, torch.int32, ntensors + 1, "tensor_first", "ntensors + 1 = ")
+    _check_lamb_buffer(group_of_tensor, torch.int32, ntensors, "group_of_tensor", "")
     _check_lamb_buffer(trust, torch.float32, ntensors, "trust")
-    if partial is None or partial.dtype != torch.float64 or not partial.is_contiguous():
-        raise ValueError("partial must be a contiguous float64 device tensor")
-    _need_cuda(partial)
-    if clip is not None:
-        _check_clip(clip)
-    groups = opt_groups(specs)
+    _check_partial_sums(partial)
+    clip_p, groups = _clip_ptr(clip), opt_groups(specs)
     _lib.call("vit_lamb_trust_groups", _ptr(partial), _ptr(tensor_first), _ptr(group_of_tensor), ntensors, groups,
-              len(groups), _ptr(trust), _ptr(clip), _stream(stream))
+              len(groups), _ptr(trust), clip_p, _stream(stream))
 
 
 def lamb_update_groups(table_dev, tensor_of_chunk, trust, group_of_chunk, nchunks, specs, shadow_dtype, ema_dev=None,
@@ -811,16 +803,11 @@ def lamb_update_groups(table_dev, tensor_of_chunk, trust, group_of_chunk, nchunk
     """vit_lamb_update_groups: lamb_update() with each chunk's scalars from specs[group_of_chunk[i]], the specs
     lamb_moments_groups was given."""
     _need_cuda(table_dev)
-    _check_group_index(tensor_of_chunk, nchunks, "tensor_of_chunk")
-    _check_group_index(group_of_chunk, nchunks, "group_of_chunk")
+    _check_lamb_buffer(tensor_of_chunk, torch.int32, nchunks, "tensor_of_chunk", "")
+    _check_lamb_buffer(group_of_chunk, torch.int32, nchunks, "group_of_chunk", "")
     _check_lamb_buffer(trust, torch.float32, 1, "trust")
-    ema_w = 0.0
-    if ema_dev is not None:
-        _check_ema(ema_dev, nchunks)
-        ema_w = 1.0 - float(ema_decay)
-    if clip is not None:
-        _check_clip(clip)
-    groups = opt_groups(specs)
-    _lib.call("vit_lamb_update_groups", _ptr(table_dev), _ptr(ema_dev), _ptr(tensor_of_chunk), _ptr(trust),
-              _ptr(group_of_chunk), nchunks, groups, len(groups), dtype_code(shadow_dtype), ema_w, _ptr(clip),
+    ema_p, ema_w = _ema_args(ema_dev, ema_decay, nchunks)
+    clip_p, groups = _clip_ptr(clip), opt_groups(specs)
+    _lib.call("vit_lamb_update_groups", _ptr(table_dev), ema_p, _ptr(tensor_of_chunk), _ptr(trust),
+              _ptr(group_of_chunk), nchunks, groups, len(groups), dtype_code(shadow_dtype), ema_w, clip_p,
               _stream(stream))

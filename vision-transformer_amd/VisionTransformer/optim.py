@@ -23,6 +23,11 @@ from . import _ops
 from ._engine import shadow_of
 
 
+def _check_hyper(name, lr, eps, betas):
+    if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+        raise ValueError(f"invalid {name} hyper-parameters")
+
+
 def _check_ema_decay(ema_decay):
     if ema_decay is not None and not (0 < ema_decay < 1):
         raise ValueError(f"ema_decay must be None or lie strictly between 0 and 1 (got {ema_decay!r})")
@@ -71,14 +76,17 @@ def _closure_loss(closure):
 class _StepTable:
     """One cached launch of the fused step: the device chunk table over the parameters `params` (and, where any of
     them has an EMA, the EMA pointer array cut alike), with what valid() compares to tell that it still describes
-    them.  `keep` holds every tensor whose pointer the device table carries.  `lamb` is FusedLamb's: the tensor index
-    of the table and the buffers its three launches pass along (_LambIndex), made at the table's first LAMB step."""
+    them.  `keep` holds every tensor whose pointer the device table carries.  `sizes` is None here and the merged
+    table's own (_GroupedTable).  `lamb` is FusedLamb's: the tensor index of the table and the buffers its three
+    launches pass along (_LambIndex), made at the table's first LAMB step and None for ever under plain AdamW.  A table
+    built in the place of `old` over the very same parameters (new gradient tensors, a new EMA) inherits it: same
+    tensors, same cut, and the ratios of the last step stay readable through a skipped one."""
 
     __slots__ = ("version", "params", "grads", "grad_ptrs", "param_ptrs", "moments", "emas", "dev_tab", "ema_dev",
-                 "nchunks", "shadow_dtype", "device", "keep", "lamb")
+                 "nchunks", "shadow_dtype", "device", "keep", "lamb", "sizes")
 
     @classmethod
-    def build(cls, opt, ps):
+    def build(cls, opt, ps, old=None):
         state, tab = opt.state, cls()
         shadows = [shadow_of(p) for p in ps]
         # one shadow dtype per table, the first there is: the kernel writes no shadow of another
@@ -97,7 +105,10 @@ class _StepTable:
         else:
             tab.ema_dev, _ = _ops.build_ema_pointers(list(zip(ps, tab.emas)), tab.device)
         tab.param_ptrs, tab.grad_ptrs = [p.data_ptr() for p in ps], [g.data_ptr() for g in tab.grads]
-        tab.lamb = None
+        tab.sizes = tab.lamb = None
+        if (old is not None and old.lamb is not None and old.lamb.chunk == _ops.CHUNK and tab.device == old.device
+                and len(old.params) == len(ps) and all(a is b for a, b in zip(old.params, ps))):
+            tab.lamb = old.lamb
         return tab
 
     def lamb_index(self):
@@ -110,14 +121,15 @@ class _StepTable:
                                    torch.ones(ntensors, dtype=torch.float32, device=self.device), _ops.CHUNK)
         return self.lamb
 
-    def valid(self, opt, ps):
-        """Same optimizer version, same parameters, every parameter still holds the same .grad tensor object and the
-        same moment tensor objects as when the table was built, and no parameter's or gradient's storage moved (`p.data = ...`
-        re-points storage without changing any object identity).  Two data_ptr() per parameter plus
+    def valid(self, opt, ps, sizes=None):
+        """Same optimizer version, same parameters (for the merged table each group bringing as many as `sizes` says;
+        no sizes for any other), every parameter still holds the same .grad tensor object and the same moment tensor
+        objects as when the table was built, and no parameter's or gradient's storage moved (`p.data = ...` re-points
+        storage without changing any object identity).  Two data_ptr() per parameter plus
         identity checks: this runs every step.  The engine's shadows change only when it rebuilds its buffers, and
         then every gradient view is a new object too.  A table built with EMA pointers also wants every parameter's
         `state[p]["ema"]` to be the tensor object it points at; one built without serves only the EMA-less step."""
-        if self.version != opt._version or len(self.params) != len(ps):
+        if self.version != opt._version or len(self.params) != len(ps) or self.sizes != sizes:
             return False
         state = opt.state
         if self.emas is None:      # a table without EMA pointers serves only the EMA-less step (no per-parameter work)
@@ -140,14 +152,15 @@ class _GroupedTable(_StepTable):
     """The merged table of a `fuse_groups` step: the stepping parameters of every group, each group's consecutive, in
     one chunk table, with the device maps chunk -> group and tensor -> group beside it (indices modulo
     _lib.OPT_MAX_GROUPS) and `spans`, one _Span per launch of at most that many groups.  `sizes` is how many
-    parameters each group brought: with valid(), which holds unchanged, it tells that the table still describes the
-    step.  No hyper-parameter is part of it."""
+    parameters each group brought, which valid() compares too.  No hyper-parameter is part of it.  The chunks come in
+    the order the per-group tables list them, so a norm pass over this table leaves the partials, and with them the
+    norm's bits, of one over those."""
 
-    __slots__ = ("sizes", "group_of_chunk", "group_of_tensor", "spans")
+    __slots__ = ("group_of_chunk", "group_of_tensor", "spans")
 
     @classmethod
-    def build_grouped(cls, opt, ps, sizes):
-        tab = cls.build(opt, ps)
+    def build_grouped(cls, opt, ps, sizes, old=None):
+        tab = cls.build(opt, ps, old)
         tab.sizes = list(sizes)
         tab.group_of_chunk, tab.group_of_tensor, bounds = _ops.build_group_index(tab.keep, sizes, tab.device)
         if bounds[-1][1] != tab.nchunks:
@@ -255,7 +268,12 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
     `param_groups` at every step, passed to the kernel by value (include/vit_hip.h "Grouped optimizer steps"), so a
     scheduler that rewrites `group["lr"]` every step rebuilds nothing and copies nothing.  Bit for bit the per-group
     step.  A step in which some group holds parameters at different step counts (a parameter whose first gradient
-    came late), or whose parameters span devices or shadow dtypes, runs per group as with `fuse_groups` off."""
+    came late), or whose parameters span devices or shadow dtypes, runs per group as with `fuse_groups` off.
+
+    One step path: _plan() yields each group's stepping parameters by step count, _run_per_group() or _run_grouped()
+    launches them (the second falls back on the first), _norm_pass() is the clipped step's norm over whichever tables
+    there are, and _group_spec() is the one reader of a group's hyper-parameters.  A subclass changes the update by
+    overriding _group_spec(), _adamw() and _grouped_launch() (FusedLamb)."""
 
     # its kernel writes the engines' compute-dtype shadows along with the masters: no repack follows a step
     # (_engine._after_optimizer_step marks them stale after every other optimizer's)
@@ -264,8 +282,7 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
                  max_grad_norm=None, skip_nonfinite=True, ema_decay=None, fuse_groups=False):
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
-            raise ValueError("invalid AdamW hyper-parameters")
+        _check_hyper("AdamW", lr, eps, betas)
         _check_max_grad_norm(max_grad_norm)
         _check_ema_decay(ema_decay)
         self._version = 0
@@ -308,36 +325,48 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
         """How many steps were skipped for a non-finite norm so far: a fresh 0-d device tensor, as grad_norm()."""
         return self._clip_state()[3].clone()
 
-    def _clipped_launch(self, work):
-        """grad_sumsq per table into consecutive slices of one partial buffer, one finish, the clipped update per
-        table — all on the current stream, which the engine's backward() has already made wait for the weight-
-        gradient stream and the all-reduce handles."""
+    def _norm_pass(self, tabs):
+        """The clip block of a step over `tabs` (the per-group tables, or the one merged table): grad_sumsq per table
+        into consecutive slices of one partial buffer, sized here, and one finish — on the current stream, which the
+        engine's backward() has already made wait for the weight-gradient stream and the all-reduce handles."""
         _check_max_grad_norm(self.max_grad_norm)
-        device = next(tab.device for tab, _, _ in work)
-        if any(tab.device != device for tab, _, _ in work):
+        device = tabs[0].device
+        if any(tab.device != device for tab in tabs):
             raise RuntimeError("FusedAdamW: a global gradient norm needs every parameter on one device")
-        total = sum(tab.nchunks for tab, _, _ in work)
+        total = sum(tab.nchunks for tab in tabs)
         if self._partial is None or self._partial.device != device or self._partial.numel() < total:
             self._partial = torch.empty(total, dtype=torch.float64, device=device)
         clip = self._clip_state(device)
         off = 0
-        for tab, _, _ in work:
+        for tab in tabs:
             _ops.grad_sumsq(tab.dev_tab, tab.nchunks, self.grad_scale, self._partial[off:off + tab.nchunks])
             off += tab.nchunks
         _ops.grad_clip_finish(self._partial, total, self.max_grad_norm, clip, self.skip_nonfinite)
-        for tab, group, t in work:
-            self._adamw(tab, group, t, clip)
+        return clip
 
-    def _adamw(self, tab, group, t, clip=None):
-        """The update of one table's parameters, all at step count `t`."""
+    # ---- launches -----------------------------------------------------------------------------------------------
+    def _group_spec(self, group, t):
+        """A group's vit_opt_group at step count `t`: (lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2,
+        flags).  The one reader of a group's hyper-parameters: the per-group and the grouped launches take them from
+        here, read from `param_groups` at every step."""
         b1, b2 = group["betas"]
+        return (group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t, 0)
+
+    def _adamw(self, tab, spec, clip=None):
+        """The update of one table's parameters, all of the group and at the step count of `spec`."""
+        lr, b1, b2, eps, wd, bc1, bc2, _ = spec
         if self.ema_decay is not None:
-            _ops.adamw_ema(tab.dev_tab, tab.ema_dev, tab.nchunks, group["lr"], b1, b2, group["eps"],
-                           group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t, self.grad_scale, tab.shadow_dtype,
-                           self.ema_decay, clip=clip)
+            _ops.adamw_ema(tab.dev_tab, tab.ema_dev, tab.nchunks, lr, b1, b2, eps, wd, bc1, bc2, self.grad_scale,
+                           tab.shadow_dtype, self.ema_decay, clip=clip)
             return
-        _ops.adamw(tab.dev_tab, tab.nchunks, group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                   1.0 - b1 ** t, 1.0 - b2 ** t, self.grad_scale, tab.shadow_dtype, clip=clip)
+        _ops.adamw(tab.dev_tab, tab.nchunks, lr, b1, b2, eps, wd, bc1, bc2, self.grad_scale, tab.shadow_dtype,
+                   clip=clip)
+
+    def _grouped_launch(self, tab, specs, span, clip):
+        """The update of one span of the merged table, whose groups are those of `specs`."""
+        ema = self.ema_decay is not None
+        _ops.adamw_groups(span.rows, span.group_of_chunk, span.c1 - span.c0, specs, self.grad_scale, tab.shadow_dtype,
+                          ema_dev=span.ema_dev if ema else None, ema_decay=self.ema_decay if ema else None, clip=clip)
 
     # ---- step counters ------------------------------------------------------------------------------------------
     def _step_state(self, gi, group):
@@ -395,110 +424,81 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
             by_step.setdefault(host[i], []).append(ps_all[i])
         return by_step
 
-    def _table(self, key, ps):
-        """The cached table under `key` while it still describes `ps` (_StepTable.valid), else a new one in its place"""
-        tab = self._tables.get(key)
-        if tab is None or not tab.valid(self, ps):
-            tab = self._tables[key] = _StepTable.build(self, ps)
+    def _table(self, key, ps, sizes=None):
+        """The cached table under `key` while it still describes `ps` (_StepTable.valid), else a new one in its place.
+        With `sizes` (how many of `ps` each group brings) the merged table of a grouped step, or None, and nothing
+        built, where one launch cannot serve `ps`."""
+        old = self._tables.get(key)
+        if old is not None and old.valid(self, ps, sizes):
+            return old
+        if sizes is None:
+            tab = _StepTable.build(self, ps, old)
+        elif _GroupedTable.fusable(ps):
+            tab = _GroupedTable.build_grouped(self, ps, sizes, old)
+        else:
+            return None
+        self._tables[key] = tab
         return tab
+
+    def _plan(self):
+        """(gi, group, {step count: [params]}) for every group with stepping parameters, in order, its state made and
+        its counters advanced.  A generator: the unclipped per-group step launches group k before group k + 1 is
+        prepared, so the device works under the host's bookkeeping on a path that is host-bound with 28 groups."""
+        ema = self.ema_decay is not None
+        for gi, group in enumerate(self.param_groups):
+            ps_all = group["params"]
+            idx = [i for i, p in enumerate(ps_all) if p.grad is not None]
+            if not idx:
+                continue
+            if self._make_state([ps_all[i] for i in idx], ema):
+                self.invalidate()
+            yield gi, group, self._advance(gi, group, idx)
+
+    def _run_per_group(self, plan):
+        """One launch (set) per group and step count.  A clipped step's norm spans every table: it launches once they
+        all exist."""
+        clipped, work = self.max_grad_norm is not None, []
+        for gi, group, by_step in plan:
+            for t, ps in by_step.items():
+                # one table for the whole group while every parameter has the same step count, else one per count
+                tab = self._table((gi, "all") if len(by_step) == 1 else (gi, "t", t), ps)
+                if clipped:
+                    work.append((tab, group, t))
+                else:
+                    self._adamw(tab, self._group_spec(group, t))
+        if work:
+            clip = self._norm_pass([tab for tab, _, _ in work])
+            for tab, group, t in work:
+                self._adamw(tab, self._group_spec(group, t), clip)
+
+    def _run_grouped(self, plan):
+        """Every group of `plan` in one grouped launch per _lib.OPT_MAX_GROUPS groups, over one merged table (cached
+        under ("groups", "all")).  False, and nothing launched, where that cannot be: some group's stepping parameters
+        are at different step counts, or the parameters span devices or shadow dtypes."""
+        if not plan or any(len(by_step) != 1 for _, _, by_step in plan):
+            return False
+        stepping = [next(iter(by_step.values())) for _, _, by_step in plan]
+        tab = self._table(("groups", "all"), [p for ps in stepping for p in ps], [len(ps) for ps in stepping])
+        if tab is None:
+            return False
+        clip = self._norm_pass([tab]) if self.max_grad_norm is not None else None
+        specs = [self._group_spec(group, next(iter(by_step))) for _, group, by_step in plan]
+        for span in tab.spans:
+            self._grouped_launch(tab, specs[span.g0:span.g1], span, clip)
+        return True
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = _closure_loss(closure)
         self._refuse_step_while_swapped()
         _check_ema_decay(self.ema_decay)
-        if self.fuse_groups:
-            self._step_grouped()
-            return loss
-        ema, clipped, work = self.ema_decay is not None, self.max_grad_norm is not None, []
-        for gi, group in enumerate(self.param_groups):
-            ps_all = group["params"]
-            idx = [i for i, p in enumerate(ps_all) if p.grad is not None]
-            if not idx:
-                continue
-            if self._make_state([ps_all[i] for i in idx], ema):
-                self.invalidate()
-            by_step = self._advance(gi, group, idx)
-            for t, ps in by_step.items():
-                # one table for the whole group while every parameter has the same step count, else one per count
-                tab = self._table((gi, "all") if len(by_step) == 1 else (gi, "t", t), ps)
-                if clipped:      # the norm spans every table: launch once they all exist
-                    work.append((tab, group, t))
-                else:
-                    self._adamw(tab, group, t)
-        if work:
-            self._clipped_launch(work)
+        plan = self._plan()
+        if self.fuse_groups:      # the whole plan first; a step it cannot serve goes per group, as with fuse_groups off
+            plan = list(plan)
+            if self._run_grouped(plan):
+                return loss
+        self._run_per_group(plan)
         return loss
-
-    # ---- fuse_groups: every group in one launch ------------------------------------------------------------------
-    def _step_grouped(self):
-        """step() with `fuse_groups`: state and counters as ever, then one merged table over every group and one
-        grouped launch per _lib.OPT_MAX_GROUPS groups, where every group's stepping parameters share a step count
-        and all of them one device and one shadow dtype; else this step goes per group, as with `fuse_groups` off."""
-        ema, clipped, plan = self.ema_decay is not None, self.max_grad_norm is not None, []
-        for gi, group in enumerate(self.param_groups):
-            ps_all = group["params"]
-            idx = [i for i, p in enumerate(ps_all) if p.grad is not None]
-            if not idx:
-                continue
-            if self._make_state([ps_all[i] for i in idx], ema):
-                self.invalidate()
-            plan.append((gi, group, self._advance(gi, group, idx)))
-        if not plan:
-            return
-        tab = self._grouped_table(plan) if all(len(by_step) == 1 for _, _, by_step in plan) else None
-        if tab is None:
-            work = []
-            for gi, group, by_step in plan:
-                for t, ps in by_step.items():
-                    t_tab = self._table((gi, "all") if len(by_step) == 1 else (gi, "t", t), ps)
-                    if clipped:
-                        work.append((t_tab, group, t))
-                    else:
-                        self._adamw(t_tab, group, t)
-            if work:
-                self._clipped_launch(work)
-            return
-        clip = None
-        if clipped:      # the merged table lists the chunks in the order the per-group tables would: the same partials
-            _check_max_grad_norm(self.max_grad_norm)
-            if self._partial is None or self._partial.device != tab.device or self._partial.numel() < tab.nchunks:
-                self._partial = torch.empty(tab.nchunks, dtype=torch.float64, device=tab.device)
-            clip = self._clip_state(tab.device)
-            _ops.grad_sumsq(tab.dev_tab, tab.nchunks, self.grad_scale, self._partial[:tab.nchunks])
-            _ops.grad_clip_finish(self._partial, tab.nchunks, self.max_grad_norm, clip, self.skip_nonfinite)
-        specs = [self._group_spec(group, next(iter(by_step))) for _, group, by_step in plan]
-        for span in tab.spans:
-            self._grouped_launch(tab, specs[span.g0:span.g1], span, clip)
-
-    def _grouped_table(self, plan):
-        """The merged table of `plan` (cached under its own key, valid as any _StepTable is and while each group brings
-        as many parameters as it did), or None where one launch cannot serve its parameters."""
-        ps = [p for _, _, by_step in plan for p in next(iter(by_step.values()))]
-        sizes = [len(next(iter(by_step.values()))) for _, _, by_step in plan]
-        key = ("groups", "all")
-        old = self._tables.get(key)
-        if old is not None and old.sizes == sizes and old.valid(self, ps):
-            return old
-        if not _GroupedTable.fusable(ps):
-            return None
-        tab = self._tables[key] = _GroupedTable.build_grouped(self, ps, sizes)
-        # as FusedLamb._table: the same parameters cut alike keep the tensor index, its buffers and the last ratios
-        if (old is not None and old.lamb is not None and old.lamb.chunk == _ops.CHUNK and tab.device == old.device
-                and len(old.params) == len(ps) and all(a is b for a, b in zip(old.params, ps))):
-            tab.lamb = old.lamb
-        return tab
-
-    def _group_spec(self, group, t):
-        """A group's vit_opt_group at step count `t`: the scalars _adamw() passes."""
-        b1, b2 = group["betas"]
-        return (group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t, 0)
-
-    def _grouped_launch(self, tab, specs, span, clip):
-        """The update of one span of the merged table, whose groups are those of `specs`."""
-        ema = self.ema_decay is not None
-        _ops.adamw_groups(span.rows, span.group_of_chunk, span.c1 - span.c0, specs, self.grad_scale, tab.shadow_dtype,
-                          ema_dev=span.ema_dev if ema else None, ema_decay=self.ema_decay if ema else None, clip=clip)
 
     # ---- weight EMA ---------------------------------------------------------------------------------------------
     def _ema_params(self):
@@ -527,6 +527,7 @@ class FusedAdamW(_EmaSurface, torch.optim.Optimizer):
 
 
 _LAMB_GROUP_KEYS = ("always_adapt", "trust_clip")
+_ADAPT, _TRUST_CLIP = _ops._lib.OPT_ADAPT, _ops._lib.OPT_TRUST_CLIP      # a spec's flag bits (vit_opt_group.flags)
 
 
 def _as_f32(x):
@@ -540,7 +541,26 @@ def _check_lamb_flags(group):
             raise ValueError(f"{k} must be a bool (got {group[k]!r})")
 
 
-class FusedLamb(FusedAdamW):
+def _lamb_flags(always_adapt, trust_clip):
+    """The two LAMB keys of `param_groups` as a constructor's defaults, checked."""
+    flags = dict(always_adapt=always_adapt, trust_clip=trust_clip)
+    _check_lamb_flags(flags)
+    return flags
+
+
+class _LambGroups:
+    """What FusedLamb and the host path's Lamb share of the two LAMB keys: a loaded group that lacks them (a torch
+    AdamW / FusedAdamW checkpoint has neither) keeps this optimizer's current values."""
+
+    def load_state_dict(self, state_dict):
+        mine = [{k: g[k] for k in _LAMB_GROUP_KEYS} for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, kept in zip(self.param_groups, mine):
+            for k, v in kept.items():
+                group.setdefault(k, v)
+
+
+class FusedLamb(_LambGroups, FusedAdamW):
     """LAMB (timm's Lamb / NVIDIA's FusedLAMB, bias correction on; the reference has none) over FusedAdamW's tables,
     counters, clipping, EMA and swap: only the per-table launch differs.  For a tensor w of a group at step count t
 
@@ -561,8 +581,7 @@ class FusedLamb(FusedAdamW):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, always_adapt=False,
                  trust_clip=False, grad_scale=1.0, max_grad_norm=None, skip_nonfinite=True, ema_decay=None,
                  fuse_groups=False):
-        flags = dict(always_adapt=always_adapt, trust_clip=trust_clip)
-        _check_lamb_flags(flags)
+        flags = _lamb_flags(always_adapt, trust_clip)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
                          fuse_groups=fuse_groups)
@@ -572,57 +591,34 @@ class FusedLamb(FusedAdamW):
                 group.setdefault(k, v)
         self._stepped = []        # the tables of the last step, for trust_ratios()
 
-    def load_state_dict(self, state_dict):
-        mine = [{k: g[k] for k in _LAMB_GROUP_KEYS} for g in self.param_groups]
-        super().load_state_dict(state_dict)
-        for group, kept in zip(self.param_groups, mine):      # a torch AdamW / FusedAdamW checkpoint has neither key
-            for k, v in kept.items():
-                group.setdefault(k, v)
-
     @torch.no_grad()
     def step(self, closure=None):
         self._stepped = []        # (not in invalidate(): a later group's fresh state invalidates in mid-step)
         return super().step(closure)
 
-    def _table(self, key, ps):
-        """FusedAdamW's, and a table rebuilt over the very same parameters (new gradient tensors, a new EMA) inherits
-        the tensor index and buffers of the one it replaces: same tensors, same cut, and the ratios of the last step
-        stay readable through a skipped one."""
-        old = self._tables.get(key)
-        tab = super()._table(key, ps)
-        if (tab is not old and old is not None and old.lamb is not None and old.lamb.chunk == _ops.CHUNK
-                and tab.device == old.device and len(old.params) == len(ps)
-                and all(a is b for a, b in zip(old.params, ps))):
-            tab.lamb = old.lamb
-        return tab
-
-    def _adamw(self, tab, group, t, clip=None):
-        """The LAMB update of one table's parameters, all at step count `t`."""
+    def _group_spec(self, group, t):
+        """FusedAdamW's with the betas as the kernels receive them, rounded to fp32, and the group's flags."""
         _check_lamb_flags(group)
-        # The betas as the kernels receive them, rounded to fp32: the recurrence runs with 1 - fl32(b2), which is
-        # 1.3e-5 (relative) away from 1 - 0.999, so bias corrections formed from the unrounded betas would leave
-        # sqrt(v_hat), u and with it every ratio off by 6e-6 in the first steps.  From the rounded ones the step is
-        # exactly LAMB with betas 1e-8 away from the group's.
-        b1, b2 = (_as_f32(b) for b in group["betas"])
-        eps, wd, bc1, bc2 = group["eps"], group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t
+        # The recurrence runs with 1 - fl32(b2), which is 1.3e-5 (relative) away from 1 - 0.999, so bias corrections
+        # formed from the unrounded betas would leave sqrt(v_hat), u and with it every ratio off by 6e-6 in the first
+        # steps.  From the rounded ones the step is exactly LAMB with betas 1e-8 away from the group's.
+        b1, b2 = group["betas"]
+        b1, b2, wd = _as_f32(b1), _as_f32(b2), group["weight_decay"]
+        flags = (_ADAPT if wd != 0 or group["always_adapt"] else 0) | (_TRUST_CLIP if group["trust_clip"] else 0)
+        return (group["lr"], b1, b2, group["eps"], wd, 1.0 - b1 ** t, 1.0 - b2 ** t, flags)
+
+    def _adamw(self, tab, spec, clip=None):
+        """The three LAMB launches over one table's parameters, all of the group and at the step count of `spec`."""
+        lr, b1, b2, eps, wd, bc1, bc2, flags = spec
         ix = tab.lamb_index()
         ema = self.ema_decay is not None
         _ops.lamb_moments(tab.dev_tab, tab.nchunks, b1, b2, eps, wd, bc1, bc2, self.grad_scale, ix.partial, clip=clip)
-        _ops.lamb_trust(ix.partial, ix.tensor_first, ix.ntensors, ix.trust,
-                        adapt=wd != 0 or group["always_adapt"], trust_clip=group["trust_clip"], clip=clip)
-        _ops.lamb_update(tab.dev_tab, ix.tensor_of_chunk, ix.trust, tab.nchunks, group["lr"], eps, wd, bc1, bc2,
+        _ops.lamb_trust(ix.partial, ix.tensor_first, ix.ntensors, ix.trust, adapt=flags & _ADAPT,      # truth values
+                        trust_clip=flags & _TRUST_CLIP, clip=clip)
+        _ops.lamb_update(tab.dev_tab, ix.tensor_of_chunk, ix.trust, tab.nchunks, lr, eps, wd, bc1, bc2,
                          tab.shadow_dtype, ema_dev=tab.ema_dev if ema else None,
                          ema_decay=self.ema_decay if ema else None, clip=clip)
         self._stepped.append(tab)
-
-    def _group_spec(self, group, t):
-        """A group's vit_opt_group at step count `t`: the scalars _adamw() passes, the betas rounded as there."""
-        _check_lamb_flags(group)
-        b1, b2 = (_as_f32(b) for b in group["betas"])
-        wd = group["weight_decay"]
-        flags = ((_ops._lib.OPT_ADAPT if wd != 0 or group["always_adapt"] else 0)
-                 | (_ops._lib.OPT_TRUST_CLIP if group["trust_clip"] else 0))
-        return (group["lr"], b1, b2, group["eps"], wd, 1.0 - b1 ** t, 1.0 - b2 ** t, flags)
 
     def _grouped_launch(self, tab, specs, span, clip):
         """The three LAMB launches over one span of the merged table.  The partials, the tensor index and the ratios
@@ -828,7 +824,7 @@ class EmaAdamW(_EmaSurface, _HostClip, torch.optim.AdamW):
         self._ema_swapped = not self._ema_swapped
 
 
-class Lamb(_EmaSurface, _HostClip, torch.optim.Optimizer):
+class Lamb(_LambGroups, _EmaSurface, _HostClip, torch.optim.Optimizer):
     """The host path's counterpart of FusedLamb, in torch ops on whatever device and dtype the parameters have: the
     same formulas (FusedLamb's docstring), defaults, `param_groups` keys and state keys, `max_grad_norm` /
     `skip_nonfinite` as ClippedAdamW has them, `ema_decay` and the swap surface as EmaAdamW, and trust_ratios().  As
@@ -836,23 +832,14 @@ class Lamb(_EmaSurface, _HostClip, torch.optim.Optimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, always_adapt=False,
                  trust_clip=False, max_grad_norm=None, skip_nonfinite=True, ema_decay=None):
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
-            raise ValueError("invalid LAMB hyper-parameters")
-        flags = dict(always_adapt=always_adapt, trust_clip=trust_clip)
-        _check_lamb_flags(flags)
+        _check_hyper("LAMB", lr, eps, betas)
+        flags = _lamb_flags(always_adapt, trust_clip)
         _check_max_grad_norm(max_grad_norm)
         _check_ema_decay(ema_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **flags))
         self.ema_decay = ema_decay
         self._init_clip(max_grad_norm, skip_nonfinite)
         self._ratios = {}
-
-    def load_state_dict(self, state_dict):
-        mine = [{k: g[k] for k in _LAMB_GROUP_KEYS} for g in self.param_groups]
-        super().load_state_dict(state_dict)
-        for group, kept in zip(self.param_groups, mine):      # a torch AdamW / FusedAdamW checkpoint has neither key
-            for k, v in kept.items():
-                group.setdefault(k, v)
 
     @torch.no_grad()
     def step(self, closure=None):

@@ -560,15 +560,25 @@ __global__ __launch_bounds__(256) void grad_clip_finish_kernel(const double* __r
   clip[3] += skip ? 1.f : 0.f;
 }
 
-// The AdamW update with the gradient scale multiplied by clip[1] (coef), and no access to p / m / v / shadow at all
-// when clip[2] (skip) is set.  A kernel of its own, so adamw_kernel keeps its arguments and its code.
+// How every kernel of a clipped step begins: false when clip[2] (skip) is set, and the kernel then returns before it
+// touches anything; else the gradient scale, where the kernel has one, takes clip[1] (coef).  clip == NULL is the
+// unclipped step.
+VIT_DEV bool clip_enter(const float* __restrict__ clip, float* gscale = nullptr) {
+  if (!clip) return true;
+  if (clip[2] != 0.f) return false;
+  if (gscale) *gscale = *gscale * clip[1];
+  return true;
+}
+
+// The AdamW update of a clipped step.  A kernel of its own, so adamw_kernel keeps its arguments and its code.  Its
+// clip is never NULL (vit_adamw_clipped refuses one), so clip_enter's first exit is dead code here.
 template <class TS>
 __global__ __launch_bounds__(256) void adamw_clipped_kernel(const vit_tensor_chunk* __restrict__ tab, float lr,
                                                             float b1, float b2, float eps, float wd, float step_size,
                                                             float inv_sqrt_bc2, float gscale,
                                                             const float* __restrict__ clip) {
-  if (clip[2] != 0.f) return;
-  adamw_chunk<TS>(tab[blockIdx.x], lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale * clip[1]);
+  if (!clip_enter(clip, &gscale)) return;
+  adamw_chunk<TS>(tab[blockIdx.x], lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -583,10 +593,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const vit_tensor_chunk* 
                                                         float* const* __restrict__ ema, float lr, float b1, float b2,
                                                         float eps, float wd, float step_size, float inv_sqrt_bc2,
                                                         float gscale, float ema_w, const float* __restrict__ clip) {
-  if (clip) {
-    if (clip[2] != 0.f) return;
-    gscale = gscale * clip[1];
-  }
+  if (!clip_enter(clip, &gscale)) return;
   const vit_tensor_chunk ch = tab[blockIdx.x];
   float* const ema_p = ema[blockIdx.x];
   if (!ema_p) {
@@ -628,18 +635,11 @@ VIT_DEV float lamb_u(float m, float v, float p, float c1, float c2, float wd) {
 }
 
 // Pass 1, one workgroup per chunk: m and v as adamw_chunk forms them, written back; partial[2i] = sum p^2 and
-// partial[2i + 1] = sum u^2 over chunk i, each fp32 value squared and added in fp64, a lane's elements in index
-// order, then block_sum_f64's fixed tree.  p is only read.  clip as in adamw_ema_kernel.
-__global__ __launch_bounds__(256) void lamb_moments_kernel(const vit_tensor_chunk* __restrict__ tab, float b1, float b2,
-                                                           float c1, float c2, float wd, float gscale,
-                                                           const float* __restrict__ clip,
-                                                           double* __restrict__ partial) {
+// partial[2i + 1] = sum u^2 over chunk i = blockIdx.x, each fp32 value squared and added in fp64, a lane's elements in
+// index order, then block_sum_f64's fixed tree.  p is only read.
+VIT_DEV void lamb_moments_chunk(const vit_tensor_chunk ch, float b1, float b2, float c1, float c2, float wd,
+                                float gscale, double* __restrict__ partial) {
   __shared__ double red_p[4], red_u[4];
-  if (clip) {
-    if (clip[2] != 0.f) return;
-    gscale = gscale * clip[1];
-  }
-  const vit_tensor_chunk ch = tab[blockIdx.x];
   double sp = 0.0, su = 0.0;
   for (int64_t t = threadIdx.x; t < ch.n; t += 256) {
     const float g = ch.g[t] * gscale;
@@ -661,15 +661,22 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const vit_tensor_chun
   }
 }
 
+// clip as in adamw_ema_kernel.
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const vit_tensor_chunk* __restrict__ tab, float b1, float b2,
+                                                           float c1, float c2, float wd, float gscale,
+                                                           const float* __restrict__ clip,
+                                                           double* __restrict__ partial) {
+  if (!clip_enter(clip, &gscale)) return;
+  lamb_moments_chunk(tab[blockIdx.x], b1, b2, c1, c2, wd, gscale, partial);
+}
+
 // One workgroup per tensor: its chunks are first[b] .. first[b + 1] - 1 of pass 1's table.  Thread i adds partials
 // first + i, first + i + 256, ... in that order, then the fixed tree, as grad_clip_finish_kernel does, so a tensor
 // of more than 256 chunks takes the same path.  trust[b] = |p| / |u| where `adapt` is set and both norms are positive,
 // else 1; at most 1 with `trust_clip`.  The quotient is formed in fp64 and rounded to fp32 once.
-__global__ __launch_bounds__(256) void lamb_trust_kernel(const double* __restrict__ partial,
-                                                         const int32_t* __restrict__ first, int adapt, int trust_clip,
-                                                         float* __restrict__ trust, const float* __restrict__ clip) {
+VIT_DEV void lamb_trust_tensor(const double* __restrict__ partial, const int32_t* __restrict__ first, int adapt,
+                               int trust_clip, float* __restrict__ trust) {
   __shared__ double red_p[4], red_u[4];
-  if (clip && clip[2] != 0.f) return;
   const int64_t lo = first[blockIdx.x], hi = first[blockIdx.x + 1];
   double sp = 0.0, su = 0.0;
   for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
@@ -683,6 +690,13 @@ __global__ __launch_bounds__(256) void lamb_trust_kernel(const double* __restric
   if (adapt && sp > 0.0 && su > 0.0) r = (float)(sqrt(sp) / sqrt(su));      // a NaN sum compares false: r stays 1
   if (trust_clip && r > 1.f) r = 1.f;
   trust[blockIdx.x] = r;
+}
+
+__global__ __launch_bounds__(256) void lamb_trust_kernel(const double* __restrict__ partial,
+                                                         const int32_t* __restrict__ first, int adapt, int trust_clip,
+                                                         float* __restrict__ trust, const float* __restrict__ clip) {
+  if (!clip_enter(clip)) return;
+  lamb_trust_tensor(partial, first, adapt, trust_clip, trust);
 }
 
 // Pass 2, one workgroup per chunk: p -= (lr * trust[tensor of the chunk]) * u with u formed again by lamb_u, the
@@ -709,7 +723,7 @@ __global__ __launch_bounds__(256) void lamb_update_kernel(const vit_tensor_chunk
                                                           const float* __restrict__ trust, float lr, float c1,
                                                           float c2, float wd, float ema_w,
                                                           const float* __restrict__ clip) {
-  if (clip && clip[2] != 0.f) return;
+  if (!clip_enter(clip)) return;
   const vit_tensor_chunk ch = tab[blockIdx.x];
   const float step = lr * trust[tensor_of_chunk[blockIdx.x]];
   float* const ema_p = ema ? ema[blockIdx.x] : nullptr;
@@ -719,13 +733,13 @@ __global__ __launch_bounds__(256) void lamb_update_kernel(const vit_tensor_chunk
 
 // ---------------------------------------------------------------------------------------------------------------
 // Grouped steps (vit_hip.h "Grouped optimizer steps"): the kernels above with the launch scalars of up to
-// VIT_OPT_MAX_GROUPS param groups in ONE launch.  The per-group factors, formed on the host exactly as adamw_factors
-// and lamb_factors form them, travel by value in the kernel-argument segment (CsBatch above is the precedent), so a
-// learning rate that changes every step costs no copy.  group_of_chunk[blockIdx.x] is made wave-uniform with
-// readfirstlane before it indexes the struct: the factors then come by scalar loads from the kernel arguments, and
-// the struct is never copied to private memory.  A chunk (or tensor) whose group index is not below `n` returns
-// without touching anything.  The element arithmetic is the device functions above, called as the single-group
-// kernels call them, so every chunk comes out bit for bit as from its group's own launch.
+// VIT_OPT_MAX_GROUPS param groups in ONE launch.  The per-group factors, formed on the host by adamw_factors and
+// lamb_factors as for a single group, travel by value in the kernel-argument segment (CsBatch above is the
+// precedent), so a learning rate that changes every step costs no copy.  group_of_chunk[blockIdx.x] is made
+// wave-uniform with readfirstlane before it indexes the struct: the factors then come by scalar loads from the kernel
+// arguments, and the struct is never copied to private memory.  A chunk (or tensor) whose group index is not below
+// `n` returns without touching anything.  The element arithmetic is the device functions above, called as the
+// single-group kernels call them, so every chunk comes out bit for bit as from its group's own launch.
 // ---------------------------------------------------------------------------------------------------------------
 struct AdamwGroup {      // 32 bytes: one 8-dword scalar load
   float lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, pad;
@@ -750,10 +764,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(const vit_tensor_chun
                                                            const int32_t* __restrict__ group_of_chunk,
                                                            const AdamwGroups gs, float gscale, float ema_w,
                                                            const float* __restrict__ clip) {
-  if (clip) {
-    if (clip[2] != 0.f) return;
-    gscale = gscale * clip[1];
-  }
+  if (!clip_enter(clip, &gscale)) return;
   const unsigned gi = (unsigned)__builtin_amdgcn_readfirstlane(group_of_chunk[blockIdx.x]);
   if (gi >= (unsigned)gs.n) return;
   const AdamwGroup& h = gs.g[gi];
@@ -766,67 +777,29 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(const vit_tensor_chun
   adamw_chunk<TS, true>(ch, h.lr, h.b1, h.b2, h.eps, h.wd, h.step_size, h.inv_sqrt_bc2, gscale, ema_p, ema_w);
 }
 
-// lamb_moments_kernel's body with the group's factors.
+// lamb_moments_kernel with the group's factors.
 __global__ __launch_bounds__(256) void lamb_moments_groups_kernel(const vit_tensor_chunk* __restrict__ tab,
                                                                   const int32_t* __restrict__ group_of_chunk,
                                                                   const LambGroups gs, float gscale,
                                                                   const float* __restrict__ clip,
                                                                   double* __restrict__ partial) {
-  __shared__ double red_p[4], red_u[4];
-  if (clip) {
-    if (clip[2] != 0.f) return;
-    gscale = gscale * clip[1];
-  }
+  if (!clip_enter(clip, &gscale)) return;
   const unsigned gi = (unsigned)__builtin_amdgcn_readfirstlane(group_of_chunk[blockIdx.x]);
   if (gi >= (unsigned)gs.n) return;
   const LambGroup& h = gs.g[gi];
-  const float b1 = h.b1, b2 = h.b2, c1 = h.c1, c2 = h.c2, wd = h.wd;
-  const vit_tensor_chunk ch = tab[blockIdx.x];
-  double sp = 0.0, su = 0.0;
-  for (int64_t t = threadIdx.x; t < ch.n; t += 256) {
-    const float g = ch.g[t] * gscale;
-    float m = ch.m[t], v = ch.v[t];
-    const float p = ch.p[t];
-    m = __builtin_fmaf(b1, m, (1.0f - b1) * g);
-    v = __builtin_fmaf(b2, v, (1.0f - b2) * g * g);
-    const float u = lamb_u(m, v, p, c1, c2, wd);
-    ch.m[t] = m;
-    ch.v[t] = v;
-    sp += (double)p * (double)p;
-    su += (double)u * (double)u;
-  }
-  sp = block_sum_f64(sp, red_p);
-  su = block_sum_f64(su, red_u);
-  if (threadIdx.x == 0) {
-    partial[2 * (int64_t)blockIdx.x] = sp;
-    partial[2 * (int64_t)blockIdx.x + 1] = su;
-  }
+  lamb_moments_chunk(tab[blockIdx.x], h.b1, h.b2, h.c1, h.c2, h.wd, gscale, partial);
 }
 
-// lamb_trust_kernel's body with the flags of the tensor's group.
+// lamb_trust_kernel with the flags of the tensor's group.
 __global__ __launch_bounds__(256) void lamb_trust_groups_kernel(const double* __restrict__ partial,
                                                                 const int32_t* __restrict__ first,
                                                                 const int32_t* __restrict__ group_of_tensor,
                                                                 const LambGroups gs, float* __restrict__ trust,
                                                                 const float* __restrict__ clip) {
-  __shared__ double red_p[4], red_u[4];
-  if (clip && clip[2] != 0.f) return;
+  if (!clip_enter(clip)) return;
   const unsigned gi = (unsigned)__builtin_amdgcn_readfirstlane(group_of_tensor[blockIdx.x]);
   if (gi >= (unsigned)gs.n) return;
-  const int adapt = gs.g[gi].adapt, trust_clip = gs.g[gi].trust_clip;
-  const int64_t lo = first[blockIdx.x], hi = first[blockIdx.x + 1];
-  double sp = 0.0, su = 0.0;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-    sp += partial[2 * i];
-    su += partial[2 * i + 1];
-  }
-  sp = block_sum_f64(sp, red_p);
-  su = block_sum_f64(su, red_u);
-  if (threadIdx.x != 0) return;
-  float r = 1.f;
-  if (adapt && sp > 0.0 && su > 0.0) r = (float)(sqrt(sp) / sqrt(su));
-  if (trust_clip && r > 1.f) r = 1.f;
-  trust[blockIdx.x] = r;
+  lamb_trust_tensor(partial, first, gs.g[gi].adapt, gs.g[gi].trust_clip, trust);
 }
 
 template <class TS>
@@ -837,7 +810,7 @@ __global__ __launch_bounds__(256) void lamb_update_groups_kernel(const vit_tenso
                                                                  const int32_t* __restrict__ group_of_chunk,
                                                                  const LambGroups gs, float ema_w,
                                                                  const float* __restrict__ clip) {
-  if (clip && clip[2] != 0.f) return;
+  if (!clip_enter(clip)) return;
   const unsigned gi = (unsigned)__builtin_amdgcn_readfirstlane(group_of_chunk[blockIdx.x]);
   if (gi >= (unsigned)gs.n) return;
   const LambGroup& h = gs.g[gi];
@@ -1087,14 +1060,26 @@ extern "C" int vit_softmax_xent_mixed(const float* logits, const int64_t* labels
   return vit::check_launch("vit_softmax_xent_mixed");
 }
 
-// Host side of the chunk-table launchers.  What the three AdamW entry points check alike, reported under the name
-// `who` of the one that was called (`ptrs`: every pointer it cannot do without is set), and the two factors their
-// kernels take in place of the bias corrections.
-static int adamw_factors(const char* who, bool ptrs, int64_t nchunks, float lr, float bias_corr1, float bias_corr2,
-                         float* step_size, float* inv_sqrt_bc2) {
-  VIT_REQUIRE(ptrs && nchunks > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f, "%s: bad arguments", who);
+// Host side of the chunk-table launchers.  The two factors the AdamW kernels take in place of the bias corrections:
+// the one place that forms them, for the single-group entry points and for each group of vit_adamw_groups.
+static void adamw_factors(float lr, float bias_corr1, float bias_corr2, float* step_size, float* inv_sqrt_bc2) {
   *step_size = lr / bias_corr1;
   *inv_sqrt_bc2 = 1.0f / sqrtf(bias_corr2);
+}
+
+// What the three single-group AdamW entry points check alike, reported under the name `who` of the one that was called
+// (`ptrs`: every pointer it cannot do without is set), then adamw_factors.
+static int adamw_args(const char* who, bool ptrs, int64_t nchunks, float lr, float bias_corr1, float bias_corr2,
+                      float* step_size, float* inv_sqrt_bc2) {
+  VIT_REQUIRE(ptrs && nchunks > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f, "%s: bad arguments", who);
+  adamw_factors(lr, bias_corr1, bias_corr2, step_size, inv_sqrt_bc2);
+  return VIT_OK;
+}
+
+// The EMA weight of the entry point `who`, where it keeps an EMA at all (`used`).
+static int check_ema_weight(const char* who, bool used, float ema_weight) {
+  VIT_REQUIRE(!used || (ema_weight > 0.f && ema_weight < 1.f), "%s: ema_weight must lie in (0, 1) (got %g)", who,
+              (double)ema_weight);
   return VIT_OK;
 }
 
@@ -1108,7 +1093,7 @@ extern "C" int vit_adamw(const vit_tensor_chunk* table_dev, int64_t nchunks, flo
                          float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
                          int32_t shadow_dtype, void* stream) {
   float step_size, inv_sqrt_bc2;
-  if (int rc = adamw_factors("vit_adamw", table_dev, nchunks, lr, bias_corr1, bias_corr2, &step_size, &inv_sqrt_bc2))
+  if (int rc = adamw_args("vit_adamw", table_dev, nchunks, lr, bias_corr1, bias_corr2, &step_size, &inv_sqrt_bc2))
     return rc;
   TABLE_LAUNCH(adamw_kernel, table_dev, lr, beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2, grad_scale);
   return vit::check_launch("vit_adamw");
@@ -1134,8 +1119,8 @@ extern "C" int vit_adamw_clipped(const vit_tensor_chunk* table_dev, int64_t nchu
                                  float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
                                  float grad_scale, int32_t shadow_dtype, const float* clip, void* stream) {
   float step_size, inv_sqrt_bc2;
-  if (int rc = adamw_factors("vit_adamw_clipped", table_dev && clip, nchunks, lr, bias_corr1, bias_corr2, &step_size,
-                             &inv_sqrt_bc2))
+  if (int rc = adamw_args("vit_adamw_clipped", table_dev && clip, nchunks, lr, bias_corr1, bias_corr2, &step_size,
+                          &inv_sqrt_bc2))
     return rc;
   TABLE_LAUNCH(adamw_clipped_kernel, table_dev, lr, beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2,
                grad_scale, clip);
@@ -1147,11 +1132,10 @@ extern "C" int vit_adamw_ema(const vit_tensor_chunk* table_dev, float* const* em
                              float bias_corr2, float grad_scale, int32_t shadow_dtype, float ema_weight,
                              const float* clip, void* stream) {
   float step_size, inv_sqrt_bc2;
-  if (int rc = adamw_factors("vit_adamw_ema", table_dev && ema_dev, nchunks, lr, bias_corr1, bias_corr2, &step_size,
-                             &inv_sqrt_bc2))
+  if (int rc = adamw_args("vit_adamw_ema", table_dev && ema_dev, nchunks, lr, bias_corr1, bias_corr2, &step_size,
+                          &inv_sqrt_bc2))
     return rc;
-  VIT_REQUIRE(ema_weight > 0.f && ema_weight < 1.f, "vit_adamw_ema: ema_weight must lie in (0, 1) (got %g)",
-              (double)ema_weight);
+  if (int rc = check_ema_weight("vit_adamw_ema", true, ema_weight)) return rc;
   TABLE_LAUNCH(adamw_ema_kernel, table_dev, ema_dev, lr, beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2,
                grad_scale, ema_weight, clip);
   return vit::check_launch("vit_adamw_ema");
@@ -1164,18 +1148,23 @@ extern "C" int vit_ema_swap(const vit_tensor_chunk* table_dev, float* const* ema
   return vit::check_launch("vit_ema_swap");
 }
 
-// What vit_lamb_moments and vit_lamb_update check alike, and the two constants lamb_u takes in place of the bias
-// corrections, formed in double and rounded once each.
-static int lamb_factors(const char* who, bool ptrs, int64_t nchunks, float eps, float bias_corr1, float bias_corr2,
-                        float* c1, float* c2) {
+// The two constants lamb_u takes in place of the bias corrections, formed in double and rounded once each: the one
+// place that forms them, for vit_lamb_moments / vit_lamb_update and for each group of their grouped forms.
+static void lamb_factors(float eps, float bias_corr1, float bias_corr2, float* c1, float* c2) {
+  *c1 = (float)((double)bias_corr1 / sqrt((double)bias_corr2));
+  *c2 = (float)((double)bias_corr1 * (double)eps);
+}
+
+// What vit_lamb_moments and vit_lamb_update check alike, then lamb_factors.
+static int lamb_args(const char* who, bool ptrs, int64_t nchunks, float eps, float bias_corr1, float bias_corr2,
+                     float* c1, float* c2) {
   VIT_REQUIRE(ptrs, "%s: null pointer", who);
   VIT_REQUIRE(nchunks > 0 && nchunks <= 0x3fffffff, "%s: nchunks must be positive (got %lld)", who,
               (long long)nchunks);
   VIT_REQUIRE(bias_corr1 > 0.f && bias_corr1 <= 1.f && bias_corr2 > 0.f && bias_corr2 <= 1.f,
               "%s: bias corrections must lie in (0, 1] (got %g, %g)", who, (double)bias_corr1, (double)bias_corr2);
   VIT_REQUIRE(eps >= 0.f, "%s: eps must not be negative (got %g)", who, (double)eps);
-  *c1 = (float)((double)bias_corr1 / sqrt((double)bias_corr2));
-  *c2 = (float)((double)bias_corr1 * (double)eps);
+  lamb_factors(eps, bias_corr1, bias_corr2, c1, c2);
   return VIT_OK;
 }
 
@@ -1183,7 +1172,7 @@ extern "C" int vit_lamb_moments(const vit_tensor_chunk* table_dev, int64_t nchun
                                 float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
                                 const float* clip, double* partial, void* stream) {
   float c1, c2;
-  if (int rc = lamb_factors("vit_lamb_moments", table_dev && partial, nchunks, eps, bias_corr1, bias_corr2, &c1, &c2))
+  if (int rc = lamb_args("vit_lamb_moments", table_dev && partial, nchunks, eps, bias_corr1, bias_corr2, &c1, &c2))
     return rc;
   lamb_moments_kernel<<<(unsigned)nchunks, 256, 0, VIT_STREAM(stream)>>>(table_dev, beta1, beta2, c1, c2, weight_decay,
                                                                          grad_scale, clip, partial);
@@ -1205,11 +1194,10 @@ extern "C" int vit_lamb_update(const vit_tensor_chunk* table_dev, float* const* 
                                float eps, float weight_decay, float bias_corr1, float bias_corr2,
                                int32_t shadow_dtype, float ema_weight, const float* clip, void* stream) {
   float c1, c2;
-  if (int rc = lamb_factors("vit_lamb_update", table_dev && tensor_of_chunk && trust, nchunks, eps, bias_corr1,
-                            bias_corr2, &c1, &c2))
+  if (int rc = lamb_args("vit_lamb_update", table_dev && tensor_of_chunk && trust, nchunks, eps, bias_corr1,
+                         bias_corr2, &c1, &c2))
     return rc;
-  VIT_REQUIRE(!ema_dev || (ema_weight > 0.f && ema_weight < 1.f),
-              "vit_lamb_update: ema_weight must lie in (0, 1) (got %g)", (double)ema_weight);
+  if (int rc = check_ema_weight("vit_lamb_update", ema_dev, ema_weight)) return rc;
   TABLE_LAUNCH(lamb_update_kernel, table_dev, ema_dev, tensor_of_chunk, trust, lr, c1, c2, weight_decay, ema_weight,
                clip);
   return vit::check_launch("vit_lamb_update");
@@ -1248,7 +1236,7 @@ static int check_opt_groups(const char* who, bool ptrs, int64_t count, const vit
   return VIT_OK;
 }
 
-// The kernel-argument struct of the LAMB passes: lamb_factors' c1 and c2 per group.
+// The kernel-argument struct of the LAMB passes, c1 and c2 per group by lamb_factors.
 static int lamb_group_args(const char* who, bool ptrs, int64_t count, const vit_opt_group* groups, int32_t ngroups,
                            LambGroups* out) {
   if (int rc = check_opt_groups(who, ptrs, count, groups, ngroups, true)) return rc;
@@ -1258,8 +1246,7 @@ static int lamb_group_args(const char* who, bool ptrs, int64_t count, const vit_
     const vit_opt_group& g = groups[i];
     LambGroup& h = out->g[i];
     h.lr = g.lr, h.b1 = g.beta1, h.b2 = g.beta2, h.wd = g.weight_decay;
-    h.c1 = (float)((double)g.bias_corr1 / sqrt((double)g.bias_corr2));
-    h.c2 = (float)((double)g.bias_corr1 * (double)g.eps);
+    lamb_factors(g.eps, g.bias_corr1, g.bias_corr2, &h.c1, &h.c2);
     h.adapt = (g.flags & VIT_OPT_ADAPT) != 0, h.trust_clip = (g.flags & VIT_OPT_TRUST_CLIP) != 0;
   }
   return VIT_OK;
@@ -1271,8 +1258,7 @@ extern "C" int vit_adamw_groups(const vit_tensor_chunk* table_dev, float* const*
                                 const float* clip, void* stream) {
   if (int rc = check_opt_groups("vit_adamw_groups", table_dev && group_of_chunk, nchunks, groups, ngroups, false))
     return rc;
-  VIT_REQUIRE(!ema_dev || (ema_weight > 0.f && ema_weight < 1.f),
-              "vit_adamw_groups: ema_weight must lie in (0, 1) (got %g)", (double)ema_weight);
+  if (int rc = check_ema_weight("vit_adamw_groups", ema_dev, ema_weight)) return rc;
   AdamwGroups gs;
   memset(&gs, 0, sizeof(gs));
   gs.n = ngroups;
@@ -1280,8 +1266,7 @@ extern "C" int vit_adamw_groups(const vit_tensor_chunk* table_dev, float* const*
     const vit_opt_group& g = groups[i];
     AdamwGroup& h = gs.g[i];
     h.lr = g.lr, h.b1 = g.beta1, h.b2 = g.beta2, h.eps = g.eps, h.wd = g.weight_decay;
-    h.step_size = g.lr / g.bias_corr1;                  // adamw_factors' two, the same floats
-    h.inv_sqrt_bc2 = 1.0f / sqrtf(g.bias_corr2);
+    adamw_factors(g.lr, g.bias_corr1, g.bias_corr2, &h.step_size, &h.inv_sqrt_bc2);
   }
   TABLE_LAUNCH(adamw_groups_kernel, table_dev, ema_dev, group_of_chunk, gs, grad_scale, ema_weight, clip);
   return vit::check_launch("vit_adamw_groups");
@@ -1320,8 +1305,7 @@ extern "C" int vit_lamb_update_groups(const vit_tensor_chunk* table_dev, float* 
   if (int rc = lamb_group_args("vit_lamb_update_groups", table_dev && tensor_of_chunk && trust && group_of_chunk,
                                nchunks, groups, ngroups, &gs))
     return rc;
-  VIT_REQUIRE(!ema_dev || (ema_weight > 0.f && ema_weight < 1.f),
-              "vit_lamb_update_groups: ema_weight must lie in (0, 1) (got %g)", (double)ema_weight);
+  if (int rc = check_ema_weight("vit_lamb_update_groups", ema_dev, ema_weight)) return rc;
   TABLE_LAUNCH(lamb_update_groups_kernel, table_dev, ema_dev, tensor_of_chunk, trust, group_of_chunk, gs, ema_weight,
                clip);
   return vit::check_launch("vit_lamb_update_groups");
