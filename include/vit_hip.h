@@ -567,6 +567,35 @@ int vit_lamb_update_groups(const vit_tensor_chunk* table_dev, float* const* ema_
                            const vit_opt_group* groups, int32_t ngroups, int32_t shadow_dtype, float ema_weight,
                            const float* clip, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Validation metrics on the device (a purely added entry point, ABI 18): top-k counts, the summed loss and the
+ * confusion matrix of a batch of logits, accumulated into device state that the host reads once, when the epoch ends
+ * (the reference's evaluate, train.py:29-44, moves an argmax to the host per batch and yields one accuracy).
+ * Per row i, with x = logits + i * ld (fp32; columns [classes, ld) are never read) and y = labels[i]:
+ *   order:     entry c precedes entry d when x[c] > x[d], or when they compare equal and c < d.  A NaN counts as
+ *              greater than every number and equal to another NaN; -0.0 equals +0.0.
+ *   pred[i]    the first entry of that order — torch.argmax on the CPU: the lowest index among the maxima, the first
+ *              NaN when there is one.  Always written.
+ *   ignored:   y outside [0, classes): rank[i] = -1, row_loss[i] = 0, counts[1] += 1, and nothing is indexed by y.
+ *   scored:    rank[i] = the number of entries that precede y (top-1 is rank == 0, that is pred == y; top-k is
+ *              rank < k, with one tie rule for both); row_loss[i] = lse(x) - x[y], formed relative to the row maximum
+ *              as vit_softmax_xent forms it; counts[0] += 1; counts[2 + rank] += 1 when rank < maxk;
+ *              confusion[y * classes + pred] += 1 when confusion is not NULL; loss_sum += row_loss[i].
+ * counts [2 + maxk] int64, loss_sum [1] fp64 and confusion [classes * classes] int64 (row = label, column =
+ * prediction) are ACCUMULATED: the caller zeroes them, and launches on one stream add to them with no host
+ * involvement.  The integers are exact; loss_sum grows by the fp64 sum of the call's fp32 row terms taken in a fixed
+ * order (no floating-point atomics), so the same calls on the same inputs give the same bits.  pred, rank and
+ * row_loss ([rows] each) are per-call outputs and the second kernel's input.  Two launches: one wave per row, then one
+ * workgroup.
+ * Refused (VIT_ERR_INVALID) before any launch: a NULL among logits, labels, pred, rank, row_loss, counts, loss_sum;
+ * rows <= 0, classes <= 0, ld < classes; maxk outside [1, min(classes, VIT_EVAL_MAXK)]; rows or classes above INT32_MAX.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define VIT_EVAL_MAXK 16
+int vit_eval_update(const float* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t classes,
+                    int32_t maxk, int64_t* pred /* [rows] */, int32_t* rank /* [rows] */, float* row_loss /* [rows] */,
+                    int64_t* counts /* [2 + maxk] */, double* loss_sum /* [1] */,
+                    int64_t* confusion /* [classes * classes] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,11 +133,13 @@ _SIGS = {
     "vit_lamb_trust_groups": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(OptGroup), _I32, _P, _P, _P]),
     "vit_lamb_update_groups": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, ctypes.POINTER(OptGroup), _I32, _I32, _F,
                                               _P, _P]),
+    "vit_eval_update": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 EPI_BDR, EPI_SLAB, EPI_GENERAL, EPI_BDRS = 3, 4, 5, 8    # VIT_EPI_* (vit_hip.h): kinds vit_gemm_kernel_choice reports
 
 DROP_PATH_MAX_LAYERS = 64    # VIT_DROP_PATH_MAX_LAYERS (vit_hip.h)
+EVAL_MAXK = 16               # VIT_EVAL_MAXK (vit_hip.h)
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 

@@ -388,6 +388,34 @@ def softmax_xent_mixed(logits, labels_a, labels_b=None, lam=None, smoothing=0.0,
     return loss, dlogits
 
 
+def eval_update(logits, labels, counts, loss_sum, confusion=None, rows=None, maxk=None, stream=None):
+    """vit_eval_update: score the first `rows` rows of `logits` (float32 [R, classes], unit column stride, any row
+    stride) against `labels` (int64, at least `rows` of them) and ACCUMULATE into `counts` (int64 [2 + maxk]),
+    `loss_sum` (float64 [1]) and `confusion` (int64 [classes, classes] or None).  Returns the call's (pred int64
+    [rows], rank int32 [rows], row_loss float32 [rows]); nothing reaches the host."""
+    _need_cuda(logits, labels, counts, loss_sum, confusion)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError("logits must be a float32 [rows, classes] tensor with unit column stride")
+    classes = logits.shape[1]
+    rows = logits.shape[0] if rows is None else int(rows)
+    ld = logits.stride(0) if logits.shape[0] > 1 else classes
+    maxk = counts.numel() - 2 if maxk is None else int(maxk)
+    if not 0 < rows <= logits.shape[0] or labels.dim() != 1 or labels.numel() < rows:
+        raise ValueError(f"rows = {rows} needs that many rows of logits and labels (got {logits.shape[0]}, "
+                         f"{labels.numel()})")
+    for name, t, dt, n in (("labels", labels, torch.int64, rows), ("counts", counts, torch.int64, 2 + maxk),
+                           ("loss_sum", loss_sum, torch.float64, 1),
+                           ("confusion", confusion, torch.int64, classes * classes)):
+        if t is not None and (t.dtype != dt or t.numel() < n or not t.is_contiguous() or t.device != logits.device):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on the logits' device")
+    pred = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    rank = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    _lib.call("vit_eval_update", _ptr(logits), ld, _ptr(labels), rows, classes, maxk, _ptr(pred), _ptr(rank),
+              _ptr(row_loss), _ptr(counts), _ptr(loss_sum), _ptr(confusion), _stream(stream))
+    return pred, rank, row_loss
+
+
 MIX_ITEM_BYTES = ctypes.sizeof(_lib.MixItem)      # vit_mix_item: int32 src, float w, int32 y0, y1, x0, x1
 _MIX_DTYPE = np.dtype([("src", "<i4"), ("w", "<f4"), ("y0", "<i4"), ("y1", "<i4"), ("x0", "<i4"), ("x1", "<i4")])
 assert _MIX_DTYPE.itemsize == MIX_ITEM_BYTES == 24

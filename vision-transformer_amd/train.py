@@ -144,6 +144,51 @@ def evaluate(model, test_loader, eval_func, avg=None):
     return float(eval_func(all_lab, all_pred, average=avg, zero_division=0.0))
 
 
+@torch.no_grad()
+def validate(model, test_loader, topk=(1, 5), confusion=True):
+    """Validation loss, top-k accuracies and the confusion matrix over `test_loader`, with no host read inside the
+    loop (not in the reference, whose evaluate() above yields one score): every batch's logits are scored on the
+    device into a metrics.DeviceMetrics, and its compute() dict — n, ignored, loss, top{k}, confusion, per-class
+    precision / recall / f1 / support, macro and weighted averages — is returned after one transfer.
+
+    Eval mode, restored afterwards.  A partial last batch is padded as evaluate() pads it and the padding is not
+    scored.  Under data parallelism every rank scores its shard, the state is all-reduced once and every rank returns
+    the whole-set result; each sample counts once: of a DistributedSampler's padded shard only the first
+    len(range(rank, len(dataset), world)) rows are scored (evaluate()'s rule)."""
+    from VisionTransformer.metrics import DeviceMetrics
+    was_training = model.training
+    model.eval()
+    pad_to = getattr(getattr(model, "vit_config", None), "batch_size", None)
+    metrics = None                                    # made at the first batch: the logits name the class count
+    rank, world = _rank_world()
+    keep = None                                       # rows of this rank's shard that are samples, not sampler padding
+    s = _sampler_of(test_loader)
+    if world > 1 and isinstance(s, torch.utils.data.DistributedSampler) and not s.drop_last:
+        keep = len(range(rank, len(s.dataset), world))
+    seen = 0
+    for tensors, labels in test_loader:
+        rows = tensors.shape[0]
+        if pad_to is not None and rows < pad_to:
+            fill = tensors[-1:].expand(pad_to - rows, *tensors.shape[1:])
+            tensors = torch.cat([tensors, fill], 0)
+        logits = model(tensors.to(device, non_blocking=True))
+        if metrics is None:
+            metrics = DeviceMetrics(logits.shape[1], topk=topk, confusion=confusion, device=logits.device)
+        score = rows if keep is None else max(0, min(rows, keep - seen))
+        seen += rows
+        if score:
+            metrics.update(logits, labels.to(logits.device, non_blocking=True), rows=score)
+    model.train(was_training)
+    if metrics is None:                               # an empty shard still joins the all-reduce
+        classes = getattr(getattr(model, "vit_config", None), "num_classes", None)
+        if classes is None:
+            raise ValueError("validate(): the test loader yielded no batch")
+        metrics = DeviceMetrics(classes, topk=topk, confusion=confusion, device=device)
+    if world > 1:
+        metrics.all_reduce()
+    return metrics.compute()
+
+
 def _set_epoch(loader, epoch):
     """DistributedSampler.set_epoch on the loader's sampler (also behind data.DeviceBatches), so each epoch draws a
     new shard order on every rank."""
@@ -222,7 +267,7 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
           log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None, ema_decay=None,
           label_smoothing=0.0, mix=None, opt="adamw", weight_decay=1e-4, no_decay_1d=False, always_adapt=False,
           trust_clip=False, sched=None, warmup_steps=0, warmup_lr=0.0, min_lr=0.0, layer_decay=None,
-          fuse_groups=False):
+          fuse_groups=False, val_topk=None, val_confusion=False):
     """The reference training loop (train.py:60-119) on the HIP path.  Returns the last epoch's summed loss.
 
     Defaults keep the GPU busy: no host sync inside the epoch — the epoch loss is summed on the device and the per-step
@@ -264,7 +309,13 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     a host value, no sync), is logged at the loss's cadence, and the checkpoint dict gains one key, "lr_schedule",
     restored on resume.  `layer_decay`: optim.param_groups_layer_decay's groups, stepped in one launch (`fuse_groups`),
     under a constant schedule unless one is named.  `fuse_groups` alone steps whatever groups there are in one launch.
-    With none of these the optimizer, its groups, its launches and the checkpoint dict are the reference's."""
+    With none of these the optimizer, its groups, its launches and the checkpoint dict are the reference's.
+
+    `val_topk`, `val_confusion` (not in the reference, whose validation is one accuracy): with a tuple of k the
+    epoch's validation is validate() instead of evaluate() — on the EMA weights when there are any — with no host read
+    until its end.  "val?acc" is then its top-1, rounded as before, "Loss/val" and "Acc{k}/val" are logged and printed
+    beside it, and the checkpoint dict gains one key, "val_metrics": validate()'s dict, the confusion matrix as nested
+    lists.  k = 1 is always among the k.  None (the default) is the loop, the tags and the checkpoint dict above."""
     rank, world = _rank_world()
     saved_epoch = search_checkpoint(checkpoint_dir)
     torch.manual_seed(0)                              # identical init on every rank
@@ -354,12 +405,21 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
         running_loss = host_loss if reference_loop else float(loss_sum.item())
         dt = time.time() - t0
         acc = None
+        val = None
         if test_loader is not None and (reference_loop or (eval_iter and epoch % eval_iter == 0)):
-            from sklearn.metrics import accuracy_score
             with optimizer.ema_weights() if ema_decay is not None else contextlib.nullcontext():
-                acc = round(float(evaluate(model, test_loader, accuracy_score)), 2)
+                if val_topk is None:
+                    from sklearn.metrics import accuracy_score
+                    acc = round(float(evaluate(model, test_loader, accuracy_score)), 2)
+                else:
+                    val = validate(model, test_loader, topk=(1, *val_topk), confusion=val_confusion)
+                    acc = round(float(val["top1"]), 2)
             if writer is not None:
                 writer.add_scalar("val?acc", acc, epoch)
+                if val is not None:
+                    writer.add_scalar("Loss/val", val["loss"], epoch)
+                    for k in sorted({1, *val_topk}):
+                        writer.add_scalar(f"Acc{k}/val", val[f"top{k}"], epoch)
         if rank == 0:
             os.makedirs(checkpoint_dir, exist_ok=True)
             ckpt = {"epoch": epoch, "model_state_dict": model.state_dict(),
@@ -368,16 +428,41 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
                 ckpt["ema_state_dict"] = optimizer.ema_state_dict(model)
             if schedule is not None:
                 ckpt["lr_schedule"] = schedule.state_dict()
+            if val is not None:
+                from VisionTransformer.metrics import jsonable
+                ckpt["val_metrics"] = jsonable(val)
             torch.save(ckpt, os.path.join(checkpoint_dir, f"{epoch}.pt"))
             ips = nb * configs.batch_size * world / max(dt, 1e-9)
             print(f"Epoch {epoch}, curr loss: {running_loss:.4f}, mean_accuracy: {acc}, "
                   f"{nb} steps in {dt:.2f}s ({ips:.1f} img/s over {world} GPU(s))", flush=True)
+            if val is not None:
+                accs = ", ".join(f"top{k}: {val[f'top{k}']:.4f}" for k in sorted({1, *val_topk}))
+                print(f"Epoch {epoch}, val loss: {val['loss']:.4f}, {accs} over {val['n']} samples", flush=True)
             if clip:
                 skipped = int(optimizer.skipped_steps().item())
                 print(f"Epoch {epoch}, steps skipped for a non-finite gradient norm: {skipped - skipped_before}",
                       flush=True)
                 skipped_before = skipped
     return running_loss
+
+
+def eval_only(configs, test_loader, checkpoint_dir, topk=(1, 5), confusion=True, ema=False):
+    """validate() once on the newest checkpoint of `checkpoint_dir` (its "ema_state_dict" with `ema`): the compute()
+    dict with the checkpoint's epoch as "epoch".  Raises FileNotFoundError when the directory holds no checkpoint."""
+    saved_epoch = search_checkpoint(checkpoint_dir)
+    if saved_epoch is None:
+        raise FileNotFoundError(f"no checkpoint (N.pt) in {checkpoint_dir!r} to evaluate")
+    ckpt = torch.load(os.path.join(checkpoint_dir, f"{saved_epoch}.pt"), map_location="cpu", weights_only=True)
+    key = "ema_state_dict" if ema else "model_state_dict"
+    if key not in ckpt:
+        raise KeyError(f"checkpoint {saved_epoch}.pt has no {key!r} (it was trained without a weight EMA)")
+    torch.manual_seed(0)
+    model = vit.VisionTransformer(configs)
+    model.load_state_dict(ckpt[key])
+    model = model.to(device)
+    result = validate(model, test_loader, topk=topk, confusion=confusion)
+    result["epoch"] = saved_epoch
+    return result
 
 
 def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None, ema_decay=None,
@@ -484,6 +569,15 @@ def main():
     ap.add_argument("--mean", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
                     help="with --std: normalize training and test images per channel, (x - mean) / std")
     ap.add_argument("--std", type=float, nargs=3, default=None, metavar=("R", "G", "B"))
+    ap.add_argument("--val-topk", type=int, nargs="+", default=None, metavar="K",
+                    help="validate on the device: loss, top-K accuracies (top-1 always) and precision / recall, read "
+                         "once per validation, logged as Loss/val and Acc{K}/val and saved as the checkpoint's "
+                         "val_metrics (default: the reference's accuracy-only evaluate)")
+    ap.add_argument("--val-confusion", action="store_true",
+                    help="with --val-topk or --eval-only: also the confusion matrix and per-class precision / recall / f1")
+    ap.add_argument("--eval-only", action="store_true",
+                    help="load the newest checkpoint of --checkpoint-dir (its EMA weights with --ema-decay), validate "
+                         "once, print the metrics as one JSON line and exit")
     ap.add_argument("--reference-loop", action="store_true",
                     help="the reference's loop bookkeeping exactly: validate every epoch, restart the step counter on "
                          "resume, host-summed loss (train.py:60-119)")
@@ -592,10 +686,23 @@ def main():
         # a partial last test batch is padded by evaluate() (the CLS parameter is batch-shaped)
         test_loader = torch.utils.data.DataLoader(test_set, batch_size=args.batch, num_workers=args.workers,
                                                   sampler=tsampler, drop_last=False, pin_memory=pin)
+    if args.eval_only:
+        from VisionTransformer.metrics import jsonable
+        try:
+            result = eval_only(cfg, test_loader, args.checkpoint_dir, topk=tuple({1, *(args.val_topk or ())}),
+                               confusion=args.val_confusion, ema=args.ema_decay is not None)
+        except (FileNotFoundError, KeyError) as e:
+            ap.exit(2, f"train.py --eval-only: {e}\n")
+        if rank == 0:
+            print(json.dumps(jsonable(result)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     train(cfg, train_loader, test_loader, args.epochs, args.eval_iter, args.log_dir, args.checkpoint_dir,
           lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop, max_grad_norm=args.clip_grad_norm,
           ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix, sched=args.sched,
-          warmup_steps=args.warmup_steps, warmup_lr=args.warmup_lr, min_lr=args.min_lr, **opt_args)
+          warmup_steps=args.warmup_steps, warmup_lr=args.warmup_lr, min_lr=args.min_lr,
+          val_topk=tuple(args.val_topk) if args.val_topk else None, val_confusion=args.val_confusion, **opt_args)
     if world > 1:
         dist.destroy_process_group()
 
