@@ -80,7 +80,9 @@ const char* vit_last_error(void);
  * 18 this way: vit_softmax_xent_mixed and vit_mix_batch (label smoothing, mixup and CutMix), with no option name;
  * vit_augment_workspace_bytes and vit_augment_to_tensor (crop, flip, normalize, erase), with "augment_path";
  * vit_drop_path_rows, vit_gemm_rowscale and vit_gemm_kernel_choice (stochastic depth), with no option name;
- * vit_adamw_groups and vit_lamb_{moments,trust,update}_groups (every param group in one launch), with no option name.
+ * vit_adamw_groups and vit_lamb_{moments,trust,update}_groups (every param group in one launch), with no option name;
+ * vit_augment_to_u8, vit_randaug_workspace_bytes and vit_randaug_to_tensor (RandAugment), with no option name of their
+ * own ("augment_path" chooses the form of vit_augment_to_u8 as it does for vit_augment_to_tensor).
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -388,6 +390,99 @@ int vit_augment_to_tensor(const void* src, const int64_t* meta, const vit_aug_it
                           int64_t out_h, int64_t out_w, int64_t ksize, const float* mean3, const float* std3,
                           float erase_value, void* out, int32_t out_dtype, void* workspace, int64_t workspace_bytes,
                           void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * RandAugment between the flip and ToTensor (not in the reference; the policy is timm's `rand-m9-mstd0.5-inc1`): a
+ * chain of up to VIT_RA_MAX_LAYERS image operations per image on the uint8 RGB picture of the output size, every one
+ * bit-exact with the Pillow call it stands for.
+ *
+ * vit_augment_to_u8 is the crop, resize and flip of vit_augment_to_tensor with a uint8 store: out_u8 is
+ * [B][out_h][out_w][3] (HWC, RGB), the bytes Pillow's crop().resize().transpose(FLIP_LEFT_RIGHT) gives.  It uses the
+ * same tables, workspace, clamps, forms ("augment_path") and refusals; it neither normalizes nor erases (the erase
+ * box of the items is ignored here and applied by vit_randaug_to_tensor).
+ *
+ * vit_randaug_to_tensor takes that picture through the chains and writes the tensor.  items_dev[i] (DEVICE memory)
+ * holds image i's chain; layer l of every image runs in one launch, the kind chosen per image (uniform per
+ * workgroup):
+ *   VIT_RA_NONE          a copy
+ *   VIT_RA_AUTOCONTRAST  ImageOps.autocontrast(img): per channel lo / hi = lowest / highest value present; identity if
+ *                        hi <= lo, else table[i] = clip((int)(i * scale + offset)), scale = 255.0 / (hi - lo), offset =
+ *                        -lo * scale, in fp64, every operation rounded on its own
+ *   VIT_RA_EQUALIZE      ImageOps.equalize(img): per channel step = (pixels - count of the highest value present) /
+ *                        255; identity if step == 0 or one value only, else table[i] = min(255, (step / 2 + pixels
+ *                        below i) / step), in integers
+ *   VIT_RA_INVERT        255 - i
+ *   VIT_RA_POSTERIZE     ImageOps.posterize(img, iarg0): i & ~(2^(8 - bits) - 1), bits clamped into [0, 8]
+ *   VIT_RA_SOLARIZE      ImageOps.solarize(img, iarg0): i < thresh ? i : 255 - i, thresh clamped into [0, 256]
+ *   VIT_RA_SOLARIZE_ADD  timm's: i < iarg1 ? min(255, i + iarg0) : i, add clamped into [0, 255], thresh into [0, 256]
+ *   VIT_RA_COLOR, VIT_RA_CONTRAST, VIT_RA_BRIGHTNESS, VIT_RA_SHARPNESS
+ *                        ImageEnhance.X(img).enhance(farg) = Image.blend(degenerate, img, farg): t = d + f * (v - d) in
+ *                        fp32, the product and the sum rounded separately; for 0 <= f <= 1 truncated to uint8, else
+ *                        clipped to [0, 255] and truncated.  Degenerate d: Brightness 0; Color the gray L = (19595 R +
+ *                        38470 G + 7471 B + 0x8000) >> 16 in all channels; Contrast the constant (int)(mean(L) + 0.5),
+ *                        the mean an exact integer sum over the count in fp64; Sharpness ImageFilter.SMOOTH, the
+ *                        3x3 kernel (1 1 1; 1 5 1; 1 1 1) with every weight the fp32 quotient by 13, accumulated in
+ *                        fp32 from 0.5 row by row from the row below upward and truncated, the one-pixel border copied
+ *   VIT_RA_AFFINE        img.transform(size, AFFINE, coef, BILINEAR, fillcolor=fill), which Image.rotate also ends in:
+ *                        per output pixel, in fp64 with every operation rounded on its own, xin = a0 (x + 0.5) + a1 (y +
+ *                        0.5) + a2, yin likewise with a3..a5; the fill colour if xin is outside [0, W) or yin outside
+ *                        [0, H); else both less 0.5, x0 = floor, dx the fraction, the taps x0 and x0 + 1 clamped into
+ *                        the row, v1 = p00 + (p01 - p00) dx on row clamp(y0), v2 the same on row y0 + 1 if it exists
+ *                        (else v2 = v1), v = v1 + (v2 - v1) dy, truncated to uint8.
+ *   Any other kind acts as VIT_RA_NONE.
+ * A layer in which some image's kind needs the picture's histograms (AUTOCONTRAST, EQUALIZE, CONTRAST) is named by
+ * its bit in stats_layers and gets one launch more, before its apply launch: per such image the three channel
+ * histograms and the gray one in LDS, then that image's [3][256] uint8 table in the workspace; nothing is read on the
+ * host.  A layer whose bit is missing skips that launch and those kinds then read a stale table: a wrong picture.
+ * The last launch writes out [B][3][S_h][S_w] (fp32 / bf16) with vit_augment_to_tensor's value and erase: ((float)v /
+ * 255.0f - mean[c]) / std[c], erase_value inside erase_items_dev[i]'s box; bf16 is that value rounded once.
+ * Launches: 1 per layer + 1 per layer named in stats_layers + 1.  Nothing is allocated; layer l reads the picture
+ * layer l - 1 wrote (two uint8 pictures in the workspace take turns) and u8_in is never written.
+ * Safety: the entry point cannot read the tables.  Every tap of every kind is clamped into its image, integer
+ * arguments are clamped as stated above, an unknown kind copies: a bad table gives a wrong picture, never an access
+ * outside a buffer.  A non-finite coefficient is the caller's to refuse before the upload (it would only choose the
+ * fill colour here: comparisons with NaN fail and the pixel counts as outside).
+ * Refused: NULL u8_in / items_dev / erase_items_dev / out / workspace, B, S_h or S_w < 1, S_h or B > 65535, an image of
+ * 2^31 bytes or more, nlayers outside [1, VIT_RA_MAX_LAYERS], a stats_layers bit at or above nlayers, mean3 / std3 /
+ * erase_value / dtype as for vit_augment_to_tensor, a workspace smaller than vit_randaug_workspace_bytes, any
+ * two of out, the workspace and u8_in overlapping.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define VIT_RA_MAX_LAYERS 4
+enum {
+  VIT_RA_NONE = 0,
+  VIT_RA_AUTOCONTRAST = 1,
+  VIT_RA_EQUALIZE = 2,
+  VIT_RA_INVERT = 3,
+  VIT_RA_POSTERIZE = 4,
+  VIT_RA_SOLARIZE = 5,
+  VIT_RA_SOLARIZE_ADD = 6,
+  VIT_RA_COLOR = 7,
+  VIT_RA_CONTRAST = 8,
+  VIT_RA_BRIGHTNESS = 9,
+  VIT_RA_SHARPNESS = 10,
+  VIT_RA_AFFINE = 11,
+  VIT_RA_KINDS = 12
+};
+typedef struct vit_ra_layer {
+  double coef[6];  /* AFFINE: a0..a5 as Pillow's transform receives them */
+  int32_t kind;    /* VIT_RA_* */
+  int32_t iarg0;   /* POSTERIZE bits; SOLARIZE threshold; SOLARIZE_ADD addend */
+  int32_t iarg1;   /* SOLARIZE_ADD threshold */
+  float farg;      /* COLOR / CONTRAST / BRIGHTNESS / SHARPNESS factor */
+  uint8_t fill[4]; /* AFFINE: R, G, B of the fill colour; fill[3] unused */
+  int32_t pad_;
+} vit_ra_layer; /* 72 bytes */
+typedef struct vit_ra_item {
+  vit_ra_layer layer[VIT_RA_MAX_LAYERS];
+} vit_ra_item; /* 288 bytes */
+int vit_augment_to_u8(const void* src, const int64_t* meta, const vit_aug_item* items_dev, int64_t B, int64_t out_h,
+                      int64_t out_w, int64_t ksize, void* out_u8, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+int64_t vit_randaug_workspace_bytes(int64_t B, int64_t S_h, int64_t S_w);
+int vit_randaug_to_tensor(const void* u8_in, const vit_ra_item* items_dev, int64_t B, int64_t S_h, int64_t S_w,
+                          int32_t nlayers, int32_t stats_layers, const float* mean3, const float* std3,
+                          const vit_aug_item* erase_items_dev, float erase_value, void* out, int32_t out_dtype,
+                          void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Batch mix: mixup and CutMix of a contiguous [B][C][H][W] batch, out of place, in one streaming launch (the

@@ -61,6 +61,24 @@ class AugItem(ctypes.Structure):      # vit_aug_item, 36 bytes
     _fields_ = [(n, ctypes.c_int32) for n in ("x0", "y0", "cw", "ch", "flip", "ey0", "ey1", "ex0", "ex1")]
 
 
+class RaLayer(ctypes.Structure):      # vit_ra_layer, 72 bytes
+    _fields_ = [("coef", ctypes.c_double * 6), ("kind", ctypes.c_int32), ("iarg0", ctypes.c_int32),
+                ("iarg1", ctypes.c_int32), ("farg", ctypes.c_float), ("fill", ctypes.c_uint8 * 4),
+                ("pad_", ctypes.c_int32)]
+
+
+RA_MAX_LAYERS = 4                     # VIT_RA_MAX_LAYERS (vit_hip.h)
+
+
+class RaItem(ctypes.Structure):       # vit_ra_item, 288 bytes
+    _fields_ = [("layer", RaLayer * RA_MAX_LAYERS)]
+
+
+# VIT_RA_* kinds (vit_hip.h)
+(RA_NONE, RA_AUTOCONTRAST, RA_EQUALIZE, RA_INVERT, RA_POSTERIZE, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_COLOR, RA_CONTRAST,
+ RA_BRIGHTNESS, RA_SHARPNESS, RA_AFFINE, RA_KINDS) = range(13)
+
+
 class OptGroup(ctypes.Structure):     # vit_opt_group, 32 bytes, host memory
     _fields_ = [(n, ctypes.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "bias_corr1",
                                               "bias_corr2")] + [("flags", ctypes.c_int32)]
@@ -134,6 +152,10 @@ _SIGS = {
     "vit_lamb_update_groups": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, ctypes.POINTER(OptGroup), _I32, _I32, _F,
                                               _P, _P]),
     "vit_eval_update": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "vit_augment_to_u8": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, _P]),
+    "vit_randaug_workspace_bytes": (_I64, [_I64, _I64, _I64]),
+    "vit_randaug_to_tensor": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P, _F, _P, _I32, _P, _I64,
+                                             _P]),
 }
 
 EPI_BDR, EPI_SLAB, EPI_GENERAL, EPI_BDRS = 3, 4, 5, 8    # VIT_EPI_* (vit_hip.h): kinds vit_gemm_kernel_choice reports

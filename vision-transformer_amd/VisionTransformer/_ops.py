@@ -567,6 +567,120 @@ def augment_to_tensor(src, meta, items, out_h, out_w, ksize, out, workspace=None
     return out
 
 
+RA_ITEM_BYTES = ctypes.sizeof(_lib.RaItem)        # vit_ra_item: VIT_RA_MAX_LAYERS layers of 72 bytes
+_RA_LAYER_DTYPE = np.dtype([("coef", "<f8", (6,)), ("kind", "<i4"), ("iarg0", "<i4"), ("iarg1", "<i4"), ("farg", "<f4"),
+                            ("fill", "u1", (4,)), ("pad_", "<i4")])
+_RA_DTYPE = np.dtype([("layer", _RA_LAYER_DTYPE, (_lib.RA_MAX_LAYERS,))])
+assert _RA_LAYER_DTYPE.itemsize == ctypes.sizeof(_lib.RaLayer) == 72 and _RA_DTYPE.itemsize == RA_ITEM_BYTES == 288
+# data.RA_OPS name -> VIT_RA_* kind; the geometric ops are all the one AFFINE kind, told apart by their coefficients
+RA_KIND = {"None": _lib.RA_NONE, "AutoContrast": _lib.RA_AUTOCONTRAST, "Equalize": _lib.RA_EQUALIZE,
+           "Invert": _lib.RA_INVERT, "Posterize": _lib.RA_POSTERIZE, "Solarize": _lib.RA_SOLARIZE,
+           "SolarizeAdd": _lib.RA_SOLARIZE_ADD, "Color": _lib.RA_COLOR, "Contrast": _lib.RA_CONTRAST,
+           "Brightness": _lib.RA_BRIGHTNESS, "Sharpness": _lib.RA_SHARPNESS, "Rotate": _lib.RA_AFFINE,
+           "ShearX": _lib.RA_AFFINE, "ShearY": _lib.RA_AFFINE, "TranslateXRel": _lib.RA_AFFINE,
+           "TranslateYRel": _lib.RA_AFFINE}
+_RA_STATS_KINDS = (_lib.RA_AUTOCONTRAST, _lib.RA_EQUALIZE, _lib.RA_CONTRAST)
+
+
+def check_ra_table(table, B):
+    """The host table of vit_randaug_to_tensor, which the entry point cannot read: (op, arg, coef) = int [B, L] indices
+    into data.RA_OPS, float64 [B, L] arguments and float64 [B, L, 6] AFFINE coefficients, 1 <= L <= VIT_RA_MAX_LAYERS,
+    every argument and coefficient finite.  Returns it as a data.RaTable of int32 / float64 / float64 arrays."""
+    from .data import RA_OPS, RaTable
+    if len(table) != 3:
+        raise ValueError("randaug table: three arrays expected (op, arg, coef)")
+    op, arg, coef = np.asarray(table[0]), np.asarray(table[1], dtype=np.float64), np.asarray(table[2], dtype=np.float64)
+    if op.ndim != 2 or op.shape[0] != B or not np.issubdtype(op.dtype, np.integer):
+        raise ValueError(f"randaug table: op must be an integer [{B}, layers] array")
+    L = op.shape[1]
+    if not 1 <= L <= _lib.RA_MAX_LAYERS:
+        raise ValueError(f"randaug table: {L} layers (1 to {_lib.RA_MAX_LAYERS} allowed)")
+    if arg.shape != (B, L) or coef.shape != (B, L, 6):
+        raise ValueError(f"randaug table: arg must be [{B}, {L}] and coef [{B}, {L}, 6]")
+    if ((op < 0) | (op >= len(RA_OPS))).any():
+        raise ValueError(f"randaug table: an op outside [0, {len(RA_OPS)})")
+    if not np.isfinite(arg).all() or not np.isfinite(coef).all():
+        raise ValueError("randaug table: a non-finite argument or coefficient")
+    return RaTable(op.astype(np.int32), arg, coef)
+
+
+def _ra_kinds(op):
+    from .data import RA_OPS
+    return np.array([RA_KIND[n] for n in RA_OPS], dtype=np.int32)[op]
+
+
+def ra_stats_layers(table):
+    """The stats_layers mask of vit_randaug_to_tensor: bit l is set when some image's layer l needs the histograms."""
+    kinds = _ra_kinds(np.asarray(table[0]))
+    return sum(1 << l for l in range(kinds.shape[1]) if np.isin(kinds[:, l], _RA_STATS_KINDS).any())
+
+
+def randaug_table_host(table, fill=(128, 128, 128), pin=False):
+    """The vit_ra_item array of a checked RaTable as a uint8 host tensor (pinned with `pin`): the kind of every op, its
+    integer or fp32 argument, the AFFINE coefficients in fp64 and the fill colour."""
+    from .data import RA_OPS
+    op, arg, coef = table
+    B, L = op.shape
+    tab = np.zeros(B, dtype=_RA_DTYPE)
+    lay = tab["layer"][:, :L]
+    kinds = _ra_kinds(op)
+    lay["kind"] = kinds
+    lay["coef"] = coef
+    ints = np.isin(kinds, (_lib.RA_POSTERIZE, _lib.RA_SOLARIZE, _lib.RA_SOLARIZE_ADD))
+    lay["iarg0"] = np.where(ints, arg, 0.0).astype(np.int32)
+    lay["iarg1"] = np.where(op == RA_OPS.index("SolarizeAdd"), 128, 0)
+    lay["farg"] = arg.astype(np.float32)
+    lay["fill"][..., :3] = np.asarray(fill, dtype=np.uint8)
+    tab["layer"][:, :L] = lay
+    host = torch.empty(B * RA_ITEM_BYTES, dtype=torch.uint8, pin_memory=pin)
+    host.copy_(torch.from_numpy(tab.view(np.uint8)))
+    return host
+
+
+def augment_to_u8(src, meta, items, out_h, out_w, ksize, out, workspace=None, stream=None):
+    """vit_augment_to_u8: vit_augment_to_tensor's crop, resize and flip with a uint8 store; `out` is a contiguous uint8
+    [B, out_h, out_w, 3] device tensor (HWC, RGB).  Arguments as for augment_to_tensor; no normalize, no erase."""
+    _need_cuda(src, meta, items, out, workspace)
+    B = meta.shape[0]
+    if items.numel() * items.element_size() != B * AUG_ITEM_BYTES:
+        raise ValueError(f"augment_to_u8: the table needs {B} items of {AUG_ITEM_BYTES} bytes")
+    if tuple(out.shape) != (B, out_h, out_w, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"augment_to_u8: out must be a contiguous uint8 [{B}, {out_h}, {out_w}, 3] tensor")
+    if workspace is None:
+        workspace = torch.empty(_lib.load().vit_augment_workspace_bytes(B, out_h, out_w, ksize), dtype=torch.uint8,
+                                device=out.device)
+    _lib.call("vit_augment_to_u8", _ptr(src), _ptr(meta), _ptr(items), B, out_h, out_w, ksize, _ptr(out),
+              _ptr(workspace), workspace.numel(), _stream(stream))
+    return out
+
+
+def randaug_to_tensor(u8, ra_items, nlayers, stats_layers, erase_items, out, workspace=None, mean=None, std=None,
+                      erase_value=0.0, stream=None):
+    """vit_randaug_to_tensor: `u8` the uint8 [B, S_h, S_w, 3] picture of augment_to_u8, `ra_items` the vit_ra_item array
+    (uint8, randaug_table_host's layout), `erase_items` the vit_aug_item array whose erase boxes apply, all on the
+    device; `out` [B, 3, S_h, S_w] float32 / bfloat16.  The tables are NOT validated here (device memory; the kernels
+    clamp): data.GpuTrainTransform validates on the host before it uploads.  No allocation inside, no host sync."""
+    mean, std = check_mean_std(mean, std)
+    _need_cuda(u8, ra_items, erase_items, out, workspace)
+    if u8.dim() != 4 or u8.shape[3] != 3 or u8.dtype != torch.uint8 or not u8.is_contiguous():
+        raise ValueError("randaug_to_tensor: u8 must be a contiguous uint8 [B, S_h, S_w, 3] tensor")
+    B, sh, sw, _ = u8.shape
+    if ra_items.numel() * ra_items.element_size() != B * RA_ITEM_BYTES:
+        raise ValueError(f"randaug_to_tensor: the table needs {B} items of {RA_ITEM_BYTES} bytes")
+    if erase_items.numel() * erase_items.element_size() != B * AUG_ITEM_BYTES:
+        raise ValueError(f"randaug_to_tensor: the erase table needs {B} items of {AUG_ITEM_BYTES} bytes")
+    if tuple(out.shape) != (B, 3, sh, sw) or not out.is_contiguous():
+        raise ValueError(f"randaug_to_tensor: out must be a contiguous [{B}, 3, {sh}, {sw}] tensor")
+    if workspace is None:
+        workspace = torch.empty(_lib.load().vit_randaug_workspace_bytes(B, sh, sw), dtype=torch.uint8,
+                                device=out.device)
+    f3 = ctypes.c_float * 3
+    _lib.call("vit_randaug_to_tensor", _ptr(u8), _ptr(ra_items), B, sh, sw, int(nlayers), int(stats_layers),
+              f3(*mean) if mean else None, f3(*std) if std else None, _ptr(erase_items), float(erase_value), _ptr(out),
+              dtype_code(out), _ptr(workspace), workspace.numel(), _stream(stream))
+    return out
+
+
 def adamw(table_dev, nchunks, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale,
           shadow_dtype, stream=None, clip=None):
     """vit_adamw; with `clip` (the [4] f32 device block grad_clip_finish wrote) vit_adamw_clipped: the gradient

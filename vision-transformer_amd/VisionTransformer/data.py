@@ -21,7 +21,10 @@ Pillow), on a side stream one batch ahead of the training step.
   * `host_transform(size)` — the same transform on the host with Pillow (the CPU path, train.py --device cpu);
   * `TrainAugment(...)` / `GpuTrainTransform(size, augment, ...)` — random resized crop, horizontal flip, normalize
     and constant erase inside the resize launch (`vit_augment_to_tensor`; not in the reference), and
-    `host_train_transform(size, augment, ...)`, the same on the host.
+    `host_train_transform(size, augment, ...)`, the same on the host;
+  * `RandAugment(...)` / `RandAugment.from_config("rand-m9-mstd0.5-inc1")` — timm's policy augmentation between the
+    flip and ToTensor: `GpuTrainTransform(..., rand_augment=ra)` runs its chains on the GPU (`vit_augment_to_u8`,
+    `vit_randaug_to_tensor`), `host_train_transform(..., rand_augment=ra)` in Pillow's own calls, bit for bit the same.
 """
 import collections
 import ctypes
@@ -332,23 +335,272 @@ class TrainAugment:
         return AugTable(*(np.asarray(c, dtype=np.int32) for c in zip(*rows)))
 
 
+RA_OPS = ("None", "AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color",
+          "Contrast", "Brightness", "Sharpness", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")
+RA_MAX_LAYERS = 4       # VIT_RA_MAX_LAYERS (vit_hip.h)
+_RA_ENHANCE = ("Color", "Contrast", "Brightness", "Sharpness")
+_RA_GEOMETRIC = ("Rotate", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")
+
+RaTable = collections.namedtuple("RaTable", "op arg coef")
+
+
+class RandAugment:
+    """RandAugment's policy and draws (not in the reference; the rules are timm's `rand_augment_transform`, restated):
+    per image `num_layers` times one of `ops`, chosen uniformly with replacement, applied with probability `prob` at
+    a magnitude drawn around `magnitude` (of 10).  It sits between the flip and ToTensor: every op maps the uint8 RGB
+    picture of the output size to another one.
+
+    `draw(B, out_h, out_w)` returns the host RaTable of one batch: `op` int32 [B, num_layers] (index into RA_OPS, 0 =
+    None), `arg` float64 [B, num_layers] (the op's argument as its Pillow call takes it: degrees, shear factor,
+    translation in pixels, enhance factor, bits, threshold, addend) and `coef` float64 [B, num_layers, 6] (the AFFINE
+    coefficients Pillow receives for the geometric ops, the identity's otherwise).  Per image and layer the draws are
+    taken in this order: the op (integers(len(ops))); random() — the entry is None unless it is <= prob; the
+    magnitude (uniform(0, m) if magnitude_std is infinite, normal(m, std) if it is > 0, m otherwise; clipped to
+    [0, 10]); for an op whose level is negated at random, random() > 0.5.
+
+    Levels, with L = mag / 10: Rotate +-30 L degrees, ShearX / ShearY +-0.3 L, TranslateXRel / TranslateYRel
+    +-translate_pct L of the width / height; Color, Contrast, Brightness, Sharpness 1.8 L + 0.1, or with `increasing`
+    max(0.1, 1 +- 0.9 L); Posterize int(4 L) bits, increasing 4 - int(4 L); Solarize threshold min(256, int(256 L)),
+    increasing 256 - that; SolarizeAdd min(128, int(110 L)) below the threshold 128.
+
+    The RNG is numpy.random.default_rng([seed, rank, RandAugment.TAG]): a stream of its own, so a TrainAugment or
+    BatchMix of the same seed draws what it drew without this object beside it."""
+
+    TAG = 0x52416E64        # "RAnd": keeps this stream apart from TrainAugment's [seed, rank]
+
+    def __init__(self, num_layers=2, magnitude=9.0, magnitude_std=0.5, increasing=True, prob=0.5, translate_pct=0.45,
+                 fill=(128, 128, 128), ops=None, seed=0, rank=None):
+        if not (1 <= int(num_layers) <= RA_MAX_LAYERS) or int(num_layers) != num_layers:
+            raise ValueError(f"RandAugment: num_layers must be 1..{RA_MAX_LAYERS}")
+        if not (0.0 <= magnitude <= 10.0) or not (magnitude_std >= 0.0) or not (0.0 <= prob <= 1.0):
+            raise ValueError("RandAugment: magnitude must lie in [0, 10], magnitude_std be >= 0 and prob lie in [0, 1]")
+        if not (0.0 <= translate_pct <= 1.0):
+            raise ValueError("RandAugment: translate_pct must lie in [0, 1]")
+        fill = tuple(int(v) for v in fill)
+        if len(fill) != 3 or not all(0 <= v <= 255 for v in fill):
+            raise ValueError("RandAugment: fill must be three values in [0, 255]")
+        ops = RA_OPS[1:] if ops is None else tuple(ops)
+        if not ops or any(o not in RA_OPS[1:] for o in ops):
+            raise ValueError(f"RandAugment: ops must be a non-empty choice of {RA_OPS[1:]}")
+        if rank is None:
+            import torch.distributed as dist
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.num_layers, self.magnitude, self.magnitude_std = int(num_layers), float(magnitude), float(magnitude_std)
+        self.increasing, self.prob, self.translate_pct = bool(increasing), float(prob), float(translate_pct)
+        self.fill, self.ops = fill, ops
+        self.seed, self.rank = int(seed), int(rank)
+        self.reseed()
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        """timm's `--aa` string: 'rand' and then '-'-separated keys m (magnitude), n (layers), mstd (magnitude std;
+        >= 100 means infinite: a uniform magnitude), inc (increasing, 0 / 1) and p (probability).  A key the string
+        leaves out has timm's default for the string form — m10, n2, mstd0, inc0, p0.5 —, not the constructor's.  Further
+        keyword arguments go to the constructor and win over the string."""
+        import re
+        parts = str(config).split("-")
+        if parts[0] != "rand":
+            raise ValueError(f"RandAugment: config {config!r} does not start with 'rand'")
+        args = dict(num_layers=2, magnitude=10.0, magnitude_std=0.0, increasing=False, prob=0.5)
+        for part in parts[1:]:
+            m = re.fullmatch(r"([a-z]+)(\d+(?:\.\d*)?|\.\d+)", part)
+            if not m:
+                raise ValueError(f"RandAugment: cannot parse {part!r} in config {config!r}")
+            key, val = m.group(1), m.group(2)
+            if key == "m":
+                args["magnitude"] = float(val)
+            elif key == "n":
+                if not val.isdigit():
+                    raise ValueError(f"RandAugment: n needs an integer, not {val!r}")
+                args["num_layers"] = int(val)
+            elif key == "mstd":
+                args["magnitude_std"] = float("inf") if float(val) >= 100 else float(val)
+            elif key == "inc":
+                if val not in ("0", "1"):
+                    raise ValueError(f"RandAugment: inc is 0 or 1, not {val!r}")
+                args["increasing"] = val == "1"
+            elif key == "p":
+                args["prob"] = float(val)
+            else:
+                raise ValueError(f"RandAugment: unknown key {key!r} in config {config!r} (m, n, mstd, inc, p)")
+        return cls(**{**args, **kw})
+
+    def reseed(self, *more):
+        """Restart the stream from [seed, rank, TAG, *more] (host_train_transform: one stream per DataLoader worker)."""
+        self._rng = np.random.default_rng([self.seed, self.rank, self.TAG, *(int(v) for v in more)])
+
+    def negates(self, name):
+        """Is the level of op `name` negated at random?"""
+        return name in _RA_GEOMETRIC or (self.increasing and name in _RA_ENHANCE)
+
+    def level_arg(self, name, mag, negate=False):
+        """The argument of op `name` at magnitude `mag` (of 10); the translations' as a fraction of the size."""
+        lv = mag / 10.0
+        sign = -1.0 if negate and self.negates(name) else 1.0
+        if name == "Rotate":
+            return sign * (lv * 30.0)
+        if name in ("ShearX", "ShearY"):
+            return sign * (lv * 0.3)
+        if name in ("TranslateXRel", "TranslateYRel"):
+            return sign * (lv * self.translate_pct)
+        if name in _RA_ENHANCE:
+            return max(0.1, 1.0 + sign * (lv * 0.9)) if self.increasing else lv * 1.8 + 0.1
+        if name == "Posterize":
+            return 4 - int(lv * 4) if self.increasing else int(lv * 4)
+        if name == "Solarize":
+            t = min(256, int(lv * 256))
+            return 256 - t if self.increasing else t
+        if name == "SolarizeAdd":
+            return min(128, int(lv * 110))
+        if name in ("AutoContrast", "Equalize", "Invert", "None"):
+            return 0.0
+        raise ValueError(f"RandAugment: unknown op {name!r}")
+
+    @staticmethod
+    def coefficients(name, arg, out_h, out_w):
+        """The six AFFINE coefficients Pillow's transform receives for op `name` with argument `arg` on an out_w x
+        out_h picture (Image.rotate's own matrix for Rotate); the identity's for every other op."""
+        import math
+        if name == "ShearX":
+            return (1.0, float(arg), 0.0, 0.0, 1.0, 0.0)
+        if name == "ShearY":
+            return (1.0, 0.0, 0.0, float(arg), 1.0, 0.0)
+        if name == "TranslateXRel":
+            return (1.0, 0.0, float(arg), 0.0, 1.0, 0.0)
+        if name == "TranslateYRel":
+            return (1.0, 0.0, 0.0, 0.0, 1.0, float(arg))
+        if name != "Rotate" or arg % 360.0 == 0:
+            return (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+        angle = arg % 360.0
+        if angle in (90.0, 180.0, 270.0):
+            raise ValueError("RandAugment: Image.rotate turns by 90, 180 or 270 degrees with a transpose, not AFFINE")
+        cx, cy = out_w / 2, out_h / 2
+        angle = -math.radians(angle)
+        m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0,
+             round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+        m[2] = m[0] * -cx + m[1] * -cy + m[2]
+        m[5] = m[3] * -cx + m[4] * -cy + m[5]
+        m[2] += cx
+        m[5] += cy
+        return tuple(m)
+
+    def draw(self, B, out_h, out_w):
+        """The host RaTable of the next batch of B images of out_h x out_w (see the class)."""
+        L = self.num_layers
+        op = np.zeros((B, L), dtype=np.int32)
+        arg = np.zeros((B, L), dtype=np.float64)
+        coef = np.tile(np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), (B, L, 1))
+        rng = self._rng
+        for b in range(B):
+            for l in range(L):
+                name = self.ops[int(rng.integers(len(self.ops)))]
+                if not rng.random() <= self.prob:
+                    continue
+                mag = self.magnitude
+                if np.isinf(self.magnitude_std):
+                    mag = float(rng.uniform(0.0, mag))
+                elif self.magnitude_std > 0:
+                    mag = float(rng.normal(mag, self.magnitude_std))
+                mag = min(10.0, max(0.0, mag))
+                negate = self.negates(name) and rng.random() > 0.5
+                a = self.level_arg(name, mag, negate)
+                if name == "TranslateXRel":
+                    a = a * out_w
+                elif name == "TranslateYRel":
+                    a = a * out_h
+                op[b, l], arg[b, l] = RA_OPS.index(name), a
+                coef[b, l] = self.coefficients(name, a, out_h, out_w)
+        return RaTable(op, arg, coef)
+
+    def apply_pil(self, img, row):
+        """The chain `row` = (ops, args) of one image (one row of a RaTable's `op` and `arg`) on the RGB PIL image
+        `img`, in the literal Pillow calls: the host path, and what the kernels are bit-exact with."""
+        from PIL import Image, ImageEnhance, ImageOps
+        for k, a in zip(*row):
+            name = RA_OPS[int(k)]
+            if name == "AutoContrast":
+                img = ImageOps.autocontrast(img)
+            elif name == "Equalize":
+                img = ImageOps.equalize(img)
+            elif name == "Invert":
+                img = ImageOps.invert(img)
+            elif name == "Posterize":
+                img = img if int(a) >= 8 else ImageOps.posterize(img, int(a))
+            elif name == "Solarize":
+                img = ImageOps.solarize(img, int(a))
+            elif name == "SolarizeAdd":
+                lut = [min(255, i + int(a)) if i < 128 else i for i in range(256)]
+                img = img.point(lut + lut + lut)
+            elif name in _RA_ENHANCE:
+                img = getattr(ImageEnhance, name)(img).enhance(float(a))
+            elif name == "Rotate":
+                img = img.rotate(float(a), resample=Image.BILINEAR, fillcolor=self.fill)
+            elif name in _RA_GEOMETRIC:
+                img = img.transform(img.size, Image.AFFINE, self.coefficients(name, float(a), img.size[1], img.size[0]),
+                                    resample=Image.BILINEAR, fillcolor=self.fill)
+        return img
+
+
+def _randaug_launch(tf, packed, meta_h, table, ra, device, stream, erase_value=0.0):
+    """GpuTrainTransform with a RandAugment: vit_augment_to_u8 (crop, resize, flip), then vit_randaug_to_tensor (the
+    chains, normalize, erase) on the same stream.  Both host tables are validated BEFORE anything is uploaded, and go
+    up from fresh pinned tensors by non-blocking copies on that stream: no host sync."""
+    from . import _ops
+    sh, sw = tf.size
+    m = meta_h.numpy()
+    B = meta_h.shape[0]
+    cols = _ops.check_aug_table(table, m[:, 1], m[:, 2], sh, sw)
+    ra = _ops.check_ra_table(ra, B)
+    ks = _ops.aug_ksize(cols[2], cols[3], sh, sw)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    lib = _lib.load()
+    with torch.cuda.stream(s):
+        src = packed.to(dev, non_blocking=True)
+        meta_d = meta_h.to(dev, non_blocking=True)
+        items = _ops.aug_table_host(cols, pin=True).to(dev, non_blocking=True)
+        ra_items = _ops.randaug_table_host(ra, tf.rand_augment.fill, pin=True).to(dev, non_blocking=True)
+        need = lib.vit_augment_workspace_bytes(B, sh, sw, ks)
+        if tf._ws is None or tf._ws.numel() < need or tf._ws.device != dev:
+            tf._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=dev)
+        need = lib.vit_randaug_workspace_bytes(B, sh, sw)
+        if tf._ws_ra is None or tf._ws_ra.numel() < need or tf._ws_ra.device != dev:
+            tf._ws_ra = torch.empty(need, dtype=torch.uint8, device=dev)
+        u8 = torch.empty(B, sh, sw, 3, dtype=torch.uint8, device=dev)
+        out = torch.empty(B, 3, sh, sw, dtype=tf.dtype, device=dev)
+    _ops.augment_to_u8(src, meta_d, items, sh, sw, ks, u8, tf._ws, stream=s)
+    _ops.randaug_to_tensor(u8, ra_items, ra.op.shape[1], _ops.ra_stats_layers(ra), items, out, tf._ws_ra, mean=tf.mean,
+                           std=tf.std, erase_value=erase_value, stream=s)
+    if stream is not None:
+        for t in (src, meta_d, items, ra_items, u8, tf._ws, tf._ws_ra):
+            t.record_stream(stream)
+    return out
+
+
 class GpuTrainTransform:
     """The training transform on the GPU: RandomResizedCrop -> RandomHorizontalFlip -> ToTensor -> Normalize ->
     RandomErasing of a packed batch in ONE vit_augment_to_tensor launch (bit-exact with Pillow's crop().resize()),
     called like GpuImageTransform, so DeviceBatches takes it unchanged.  The table is drawn on the host from `meta`
-    (`augment`, a TrainAugment), validated, and uploaded by a non-blocking copy on the launch's stream."""
+    (`augment`, a TrainAugment), validated, and uploaded by a non-blocking copy on the launch's stream.
 
-    def __init__(self, size, augment, dtype=torch.float32, mean=None, std=None):
+    With `rand_augment` (a RandAugment) its chains run between the flip and ToTensor, bit-exact with Pillow's calls
+    (RandAugment.apply_pil): the crop, resize and flip store the uint8 picture (vit_augment_to_u8) and
+    vit_randaug_to_tensor takes it from there, on the same stream, still without a host sync."""
+
+    def __init__(self, size, augment, dtype=torch.float32, mean=None, std=None, rand_augment=None):
         from . import _ops
         self.size = (size, size) if isinstance(size, int) else tuple(size)
-        self.augment, self.dtype = augment, dtype
+        self.augment, self.dtype, self.rand_augment = augment, dtype, rand_augment
         self.mean, self.std = _ops.check_mean_std(mean, std)
-        self._ws = None
+        self._ws = self._ws_ra = None
 
     def __call__(self, packed, meta, device=None, stream=None):
         meta_h = _checked_meta(packed, meta)
         table = self.augment.draw(meta_h.numpy(), *self.size)
-        return _augment_launch(self, packed, meta_h, table, device, stream, erase_value=self.augment.erase_value)
+        if self.rand_augment is None:
+            return _augment_launch(self, packed, meta_h, table, device, stream, erase_value=self.augment.erase_value)
+        ra = self.rand_augment.draw(meta_h.shape[0], *self.size)
+        return _randaug_launch(self, packed, meta_h, table, ra, device, stream, erase_value=self.augment.erase_value)
 
 
 MixTable = collections.namedtuple("MixTable", "src w y0 y1 x0 x1 lam")
@@ -534,11 +786,12 @@ def host_transform(size, *, mean=None, std=None):
     return tf
 
 
-def host_train_transform(size, augment, mean=None, std=None):
+def host_train_transform(size, augment, mean=None, std=None, rand_augment=None):
     """GpuTrainTransform on the host, per item, with Pillow and torch ops (train.py --device cpu): crop().resize(),
     transpose(FLIP_LEFT_RIGHT), /255, (x - mean) / std, erase fill — the table drawn per image by `augment` (a
-    TrainAugment).  In a DataLoader worker the augment's stream is restarted once from [seed, rank, worker id, the
-    worker's seed], so the workers' copies of `augment` do not repeat each other."""
+    TrainAugment); with `rand_augment` (a RandAugment) its chain, drawn per image, runs in Pillow's own calls between
+    the flip and /255.  In a DataLoader worker the streams of both are restarted once from [seed, rank, ..., worker id,
+    the worker's seed], so the workers' copies do not repeat each other."""
     sh, sw = (size, size) if isinstance(size, int) else size
     mean_c, std_c = _mean_std_columns(mean, std)
     seeded = set()
@@ -549,6 +802,8 @@ def host_train_transform(size, augment, mean=None, std=None):
         if info is not None and info.id not in seeded:
             seeded.add(info.id)
             augment.reseed(info.id, info.seed)
+            if rand_augment is not None:
+                rand_augment.reseed(info.id, info.seed)
         if not isinstance(img, Image.Image):
             img = Image.fromarray(np.asarray(img, dtype=np.uint8))
         if img.mode != "RGB":
@@ -561,6 +816,10 @@ def host_train_transform(size, augment, mean=None, std=None):
         img = img.crop((x0, y0, x0 + cw, y0 + ch)).resize((sw, sh), Image.BILINEAR)
         if flip:
             img = img.transpose(Image.FLIP_LEFT_RIGHT)
+        if rand_augment is not None:
+            from . import _ops
+            ra = _ops.check_ra_table(rand_augment.draw(1, sh, sw), 1)
+            img = rand_augment.apply_pil(img, (ra.op[0], ra.arg[0]))
         a = np.asarray(img, dtype=np.uint8)
         x = torch.from_numpy(a.astype(np.float32) / np.float32(255.0)).permute(2, 0, 1).contiguous()
         if mean_c is not None:

@@ -116,6 +116,23 @@ VIT_DEV float gelu_erf_grad(float x) {
   return cdf + x * pdf;
 }
 
+// The value and the erase of the image path's tensor stores (vit_image.hip, vit_randaug.hip).
+struct AugNorm {        // kernel argument; on == 0: the value is v / 255
+  float mean[3], sd[3];
+  int on;
+};
+
+// ToTensor (+ Normalize): uint8 / 255, then (t - mean) / std, every operation IEEE and on its own
+VIT_DEV float aug_value(int v, float mean, float sd, bool on) {
+#pragma clang fp contract(off)
+  const float t = (float)v / 255.0f;
+  return on ? (t - mean) / sd : t;
+}
+
+VIT_DEV bool aug_erased(const vit_aug_item& it, int y, int xs) {
+  return y >= it.ey0 && y < it.ey1 && xs >= it.ex0 && xs < it.ex1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Host-side error plumbing (thread-local message, nonzero return code).
 // ---------------------------------------------------------------------------------------------------------------

@@ -126,16 +126,12 @@ __global__ __launch_bounds__(256) void resize_apply_kernel(const uint8_t* __rest
 // a mirrored store column, the normalize another final scale, the erase a pixel that reads no tap.  The tables have
 // vit_resize_to_tensor's layout.  Two apply kernels give the same bits: the direct one is resize_apply_kernel's
 // schedule; the tiled one runs the horizontal pass once per source row of a tile's row span into LDS (one dword per
-// pixel: the three clip8'd channels) and the vertical pass out of it.
+// pixel: the three clip8'd channels) and the vertical pass out of it.  Both are also instantiated with a uint8 store
+// (vit_augment_to_u8, vit_hip.h "RandAugment"): the resized, flipped crop itself as HWC bytes, no value, no erase.
 // ---------------------------------------------------------------------------------------------------------------
 // Automatic dispatch: the tiled form up to this ksize (scale <= 4, where every tile's row span fits: 16 x 4 + 2 x 4
 // rows), the range it was measured in and won (ksize 3 and 7); the direct form above it.
 constexpr int AUG_TILED_MAX_KS = 9;
-
-struct AugNorm {        // kernel argument; on == 0: the value is v / 255
-  float mean[3], sd[3];
-  int on;
-};
 
 // one axis of a crop box, clamped to its image: the origin into [0, size-1], the extent into [1, size-origin]
 VIT_DEV void clamp_box(int& o, int& n, int size) {
@@ -169,13 +165,6 @@ __global__ __launch_bounds__(256) void augment_coeffs_kernel(const int64_t* __re
   }
 }
 
-// ToTensor (+ Normalize): uint8 / 255, then (t - mean) / std, every operation IEEE and on its own
-VIT_DEV float aug_value(int v, float mean, float sd, bool on) {
-#pragma clang fp contract(off)
-  const float t = (float)v / 255.0f;
-  return on ? (t - mean) / sd : t;
-}
-
 // Pixel (x, y) of the resized crop in resize_apply_kernel's arithmetic; kwt / kht: the image's k_w / k_h tables.
 VIT_DEV void resize_pixel(const uint8_t* __restrict__ img, int W, int C, const int* __restrict__ bw,
                           const int* __restrict__ bh, const int* __restrict__ kwt, const int* __restrict__ kht, int ks,
@@ -206,8 +195,15 @@ VIT_DEV void resize_pixel(const uint8_t* __restrict__ img, int W, int C, const i
   r2 = clip8(acc2);
 }
 
-VIT_DEV bool aug_erased(const vit_aug_item& it, int y, int xs) {
-  return y >= it.ey0 && y < it.ey1 && xs >= it.ex0 && xs < it.ex1;
+// TO = uint8_t (vit_augment_to_u8) stores the resized, flipped crop itself as HWC bytes: no value table, no erase.
+template <class TO> constexpr bool AUG_BYTES = false;
+template <> constexpr bool AUG_BYTES<uint8_t> = true;
+
+VIT_DEV void aug_store_bytes(uint8_t* out, int b, int oh, int ow, int y, int xs, int v0, int v1, int v2) {
+  uint8_t* o = out + (((int64_t)b * oh + y) * ow + xs) * 3;
+  o[0] = (uint8_t)v0;
+  o[1] = (uint8_t)v1;
+  o[2] = (uint8_t)v2;
 }
 
 template <class TO>
@@ -224,11 +220,13 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const uint8_t* __res
   const int xs = it.flip ? ow - 1 - x : x;                   // column it is stored at
   const int64_t plane = (int64_t)oh * ow;
   TO* o = out + (int64_t)b * 3 * plane + (int64_t)y * ow + xs;
-  if (aug_erased(it, y, xs)) {
-    st1<TO>(o, ev);
-    st1<TO>(o + plane, ev);
-    st1<TO>(o + 2 * plane, ev);
-    return;
+  if constexpr (!AUG_BYTES<TO>) {
+    if (aug_erased(it, y, xs)) {
+      st1<TO>(o, ev);
+      st1<TO>(o + plane, ev);
+      st1<TO>(o + 2 * plane, ev);
+      return;
+    }
   }
   const ImgMeta m = reinterpret_cast<const ImgMeta*>(meta)[b];
   const int* bw = tab + b * ((int64_t)(ow + oh) * (2 + ks));
@@ -236,9 +234,13 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const uint8_t* __res
   const int* kwt = bh + 2 * oh;
   int v0, v1, v2;
   resize_pixel(src + m.off, (int)m.w, (int)m.c, bw, bh, kwt, kwt + (int64_t)ow * ks, ks, x, y, v0, v1, v2);
-  st1<TO>(o, aug_value(v0, nm.mean[0], nm.sd[0], nm.on));
-  st1<TO>(o + plane, aug_value(v1, nm.mean[1], nm.sd[1], nm.on));
-  st1<TO>(o + 2 * plane, aug_value(v2, nm.mean[2], nm.sd[2], nm.on));
+  if constexpr (AUG_BYTES<TO>) {
+    aug_store_bytes(out, b, oh, ow, y, xs, v0, v1, v2);
+  } else {
+    st1<TO>(o, aug_value(v0, nm.mean[0], nm.sd[0], nm.on));
+    st1<TO>(o + plane, aug_value(v1, nm.mean[1], nm.sd[1], nm.on));
+    st1<TO>(o + 2 * plane, aug_value(v2, nm.mean[2], nm.sd[2], nm.on));
+  }
 }
 
 // One workgroup per tile of TR output rows x TC output columns of one image; lane (lx, ly) owns column lx of the tile
@@ -268,8 +270,10 @@ __global__ __launch_bounds__(256) void augment_tiled_kernel(const uint8_t* __res
   const int* kht = kwt + (int64_t)ow * ks;
   const uint8_t* img = src + m.off;
   const int C = (int)m.c, W = (int)m.w;
+  if constexpr (!AUG_BYTES<TO>) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) val[c * 256 + threadIdx.x] = aug_value((int)threadIdx.x, nm.mean[c], nm.sd[c], nm.on);
+    for (int c = 0; c < 3; ++c) val[c * 256 + threadIdx.x] = aug_value((int)threadIdx.x, nm.mean[c], nm.sd[c], nm.on);
+  }
   int r0 = 0x7fffffff, r1 = 0;
   for (int r = 0; r < tyn; ++r) {
     const int lo = bh[2 * (ty0 + r)], n = bh[2 * (ty0 + r) + 1];
@@ -279,7 +283,7 @@ __global__ __launch_bounds__(256) void augment_tiled_kernel(const uint8_t* __res
   const bool fits = r1 - r0 <= SPAN;       // else this tile takes the direct form below
   if (fits) {
     // a column whose every pixel in this tile is erased reads nothing
-    const bool dead = xs >= it.ex0 && xs < it.ex1 && ty0 >= it.ey0 && ty0 + tyn <= it.ey1;
+    const bool dead = !AUG_BYTES<TO> && xs >= it.ex0 && xs < it.ex1 && ty0 >= it.ey0 && ty0 + tyn <= it.ey1;
     if (x < ow && !dead) {
       const int xlo = bw[2 * x], xn = bw[2 * x + 1];
       const int* kw = kwt + (int64_t)x * ks;
@@ -303,11 +307,13 @@ __global__ __launch_bounds__(256) void augment_tiled_kernel(const uint8_t* __res
   const int64_t plane = (int64_t)oh * ow;
   for (int y = ty0 + ly; y < ty0 + tyn; y += 4) {
     TO* o = out + (int64_t)b * 3 * plane + (int64_t)y * ow + xs;
-    if (aug_erased(it, y, xs)) {
-      st1<TO>(o, ev);
-      st1<TO>(o + plane, ev);
-      st1<TO>(o + 2 * plane, ev);
-      continue;
+    if constexpr (!AUG_BYTES<TO>) {
+      if (aug_erased(it, y, xs)) {
+        st1<TO>(o, ev);
+        st1<TO>(o + plane, ev);
+        st1<TO>(o + 2 * plane, ev);
+        continue;
+      }
     }
     int v0, v1, v2;
     if (fits) {
@@ -328,9 +334,13 @@ __global__ __launch_bounds__(256) void augment_tiled_kernel(const uint8_t* __res
     } else {
       resize_pixel(img, W, C, bw, bh, kwt, kht, ks, x, y, v0, v1, v2);
     }
-    st1<TO>(o, val[v0]);
-    st1<TO>(o + plane, val[256 + v1]);
-    st1<TO>(o + 2 * plane, val[512 + v2]);
+    if constexpr (AUG_BYTES<TO>) {
+      aug_store_bytes(out, b, oh, ow, y, xs, v0, v1, v2);
+    } else {
+      st1<TO>(o, val[v0]);
+      st1<TO>(o + plane, val[256 + v1]);
+      st1<TO>(o + 2 * plane, val[512 + v2]);
+    }
   }
 }
 
@@ -471,6 +481,28 @@ static void mix_batch_launch(const void* x, void* out, int64_t B, int64_t n, int
                                                    (uint32_t)H, (uint32_t)bpi, n);
 }
 
+// The coefficient launch and the apply launch (the form chosen as vit_hip.h states) of one augmented batch.
+template <class TO>
+static void augment_launch(const void* src, const int64_t* meta, const vit_aug_item* items_dev, int64_t B,
+                           int64_t out_h, int64_t out_w, int64_t ksize, const AugNorm& nm, float erase_value, TO* out,
+                           void* workspace, hipStream_t s) {
+  int* tab = (int*)workspace;
+  const int oh = (int)out_h, ow = (int)out_w, ks = (int)ksize;
+  const uint8_t* sp = (const uint8_t*)src;
+  dim3 g1((unsigned)((ow + oh + 255) / 256), (unsigned)B);
+  augment_coeffs_kernel<<<g1, 256, 0, s>>>(meta, items_dev, oh, ow, ks, tab);
+  const int64_t path = vit::opt(vit::OPT_AUGMENT_PATH);
+  const bool tiled = path == 2 || (path != 1 && ks <= AUG_TILED_MAX_KS);
+  if (tiled) {
+    dim3 g2((unsigned)((ow + VIT_AUG_TILE_COLS - 1) / VIT_AUG_TILE_COLS),
+            (unsigned)((oh + VIT_AUG_TILE_ROWS - 1) / VIT_AUG_TILE_ROWS), (unsigned)B);
+    augment_tiled_kernel<TO><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value, out);
+  } else {
+    dim3 g2((unsigned)((ow + 255) / 256), (unsigned)oh, (unsigned)B);
+    augment_apply_kernel<TO><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value, out);
+  }
+}
+
 }  // namespace
 
 extern "C" int vit_resize_ksize(int64_t in_size, int64_t out_size) {
@@ -534,32 +566,25 @@ extern "C" int vit_augment_to_tensor(const void* src, const int64_t* meta, const
   VIT_REQUIRE(workspace_bytes >= vit_augment_workspace_bytes(B, out_h, out_w, ksize),
               "vit_augment_to_tensor: workspace too small");
   hipStream_t s = VIT_STREAM(stream);
-  int* tab = (int*)workspace;
-  const int oh = (int)out_h, ow = (int)out_w, ks = (int)ksize;
-  const uint8_t* sp = (const uint8_t*)src;
-  dim3 g1((unsigned)((ow + oh + 255) / 256), (unsigned)B);
-  augment_coeffs_kernel<<<g1, 256, 0, s>>>(meta, items_dev, oh, ow, ks, tab);
-  const int64_t path = vit::opt(vit::OPT_AUGMENT_PATH);
-  const bool tiled = path == 2 || (path != 1 && ks <= AUG_TILED_MAX_KS);
-  if (tiled) {
-    dim3 g2((unsigned)((ow + VIT_AUG_TILE_COLS - 1) / VIT_AUG_TILE_COLS),
-            (unsigned)((oh + VIT_AUG_TILE_ROWS - 1) / VIT_AUG_TILE_ROWS), (unsigned)B);
-    if (out_dtype == VIT_F32)
-      augment_tiled_kernel<float><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value,
-                                                     (float*)out);
-    else
-      augment_tiled_kernel<bf16_t><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value,
-                                                      (bf16_t*)out);
-  } else {
-    dim3 g2((unsigned)((ow + 255) / 256), (unsigned)oh, (unsigned)B);
-    if (out_dtype == VIT_F32)
-      augment_apply_kernel<float><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value,
-                                                     (float*)out);
-    else
-      augment_apply_kernel<bf16_t><<<g2, 256, 0, s>>>(sp, meta, items_dev, oh, ow, ks, tab, nm, erase_value,
-                                                      (bf16_t*)out);
-  }
+  if (out_dtype == VIT_F32)
+    augment_launch<float>(src, meta, items_dev, B, out_h, out_w, ksize, nm, erase_value, (float*)out, workspace, s);
+  else
+    augment_launch<bf16_t>(src, meta, items_dev, B, out_h, out_w, ksize, nm, erase_value, (bf16_t*)out, workspace, s);
   return vit::check_launch("vit_augment_to_tensor");
+}
+
+extern "C" int vit_augment_to_u8(const void* src, const int64_t* meta, const vit_aug_item* items_dev, int64_t B,
+                                 int64_t out_h, int64_t out_w, int64_t ksize, void* out_u8, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
+  VIT_REQUIRE(src && meta && items_dev && out_u8 && workspace, "vit_augment_to_u8: null pointer");
+  VIT_REQUIRE(B > 0 && out_h > 0 && out_w > 0 && ksize >= 3, "vit_augment_to_u8: bad arguments");
+  VIT_REQUIRE(out_h <= 65535 && B <= 65535 && ksize <= 4096, "vit_augment_to_u8: size out of range");
+  VIT_REQUIRE(workspace_bytes >= vit_augment_workspace_bytes(B, out_h, out_w, ksize),
+              "vit_augment_to_u8: workspace too small");
+  const AugNorm nm = {{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, 0};
+  augment_launch<uint8_t>(src, meta, items_dev, B, out_h, out_w, ksize, nm, 0.f, (uint8_t*)out_u8, workspace,
+                          VIT_STREAM(stream));
+  return vit::check_launch("vit_augment_to_u8");
 }
 
 extern "C" int vit_mix_batch(const void* x, void* out, int32_t dtype, int64_t B, int64_t C, int64_t H, int64_t W,

@@ -566,6 +566,10 @@ def main():
     ap.add_argument("--random-erase", type=float, default=0.0, metavar="P",
                     help="probability of erasing a random box of a training image with 0 after the normalize (timm's "
                          "RandomErasing, mode const; default 0: off)")
+    ap.add_argument("--rand-augment", default=None, metavar="STR",
+                    help="RandAugment between the flip and ToTensor, as timm's --aa string, e.g. rand-m9-mstd0.5-inc1 "
+                         "(keys m, n, mstd, inc, p); needs --random-resized-crop, --hflip or --random-erase, whose "
+                         "transform it runs in; training images only (default: off)")
     ap.add_argument("--mean", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
                     help="with --std: normalize training and test images per channel, (x - mean) / std")
     ap.add_argument("--std", type=float, nargs=3, default=None, metavar=("R", "G", "B"))
@@ -630,6 +634,18 @@ def main():
         from VisionTransformer.data import TrainAugment
         augment = TrainAugment(scale=tuple(args.crop_scale) if args.random_resized_crop else None,
                                ratio=tuple(args.crop_ratio), hflip=args.hflip, erase_prob=args.random_erase)
+    rand_augment = None
+    if args.rand_augment is not None:
+        if not augmenting:
+            ap.error("--rand-augment runs inside the augmenting transform: give --random-resized-crop, --hflip or "
+                     "--random-erase with it")
+        from VisionTransformer.data import RandAugment
+        try:
+            rand_augment = RandAugment.from_config(args.rand_augment)
+        except ValueError as e:
+            ap.error(str(e))
+    # only a run with --rand-augment passes the keyword: every other run calls the transforms as it always did
+    ra_kw = {} if rand_augment is None else {"rand_augment": rand_augment}
     if args.opt != "lamb" and (args.lamb_always_adapt or args.lamb_trust_clip):
         ap.error("--lamb-always-adapt and --lamb-trust-clip need --opt lamb")
     opt_args = dict(opt=args.opt, weight_decay=args.weight_decay, no_decay_1d=args.no_decay_1d,
@@ -667,7 +683,7 @@ def main():
         from VisionTransformer import data as D
         # one transform (and coefficient workspace) per loader: each stages its batches on its own side stream
         # the augmentation is part of the resize launch, staged before the mix: erase precedes mixup, as in timm
-        train_tf = D.GpuTrainTransform(args.img, augment, mean=args.mean, std=args.std) if augment is not None \
+        train_tf = D.GpuTrainTransform(args.img, augment, mean=args.mean, std=args.std, **ra_kw) if augment is not None \
             else D.GpuImageTransform(args.img, mean=args.mean, std=args.std)
         train_loader = D.DeviceBatches(D.raw_loader(train_set, args.batch, shuffle=True, num_workers=args.workers,
                                                     sampler=sampler), train_tf, device, mix=mix)
@@ -678,7 +694,8 @@ def main():
         if args.data != "synthetic":
             from VisionTransformer import data as D
             plain = D.host_transform(args.img, mean=args.mean, std=args.std)
-            train_tf = D.host_train_transform(args.img, augment, args.mean, args.std) if augment is not None else plain
+            train_tf = D.host_train_transform(args.img, augment, args.mean, args.std, **ra_kw) if augment is not None \
+                else plain
             train_set, test_set = D.Transformed(train_set, train_tf), D.Transformed(test_set, plain)
         train_loader = torch.utils.data.DataLoader(train_set, batch_size=args.batch, shuffle=sampler is None,
                                                    sampler=sampler, num_workers=args.workers, drop_last=True,
