@@ -82,7 +82,9 @@ const char* vit_last_error(void);
  * vit_drop_path_rows, vit_gemm_rowscale and vit_gemm_kernel_choice (stochastic depth), with no option name;
  * vit_adamw_groups and vit_lamb_{moments,trust,update}_groups (every param group in one launch), with no option name;
  * vit_augment_to_u8, vit_randaug_workspace_bytes and vit_randaug_to_tensor (RandAugment), with no option name of their
- * own ("augment_path" chooses the form of vit_augment_to_u8 as it does for vit_augment_to_tensor).
+ * own ("augment_path" chooses the form of vit_augment_to_u8 as it does for vit_augment_to_tensor);
+ * vit_attn_rollout_workspace_bytes, vit_attn_rollout_step and vit_attn_rollout_step_form (attention rollout), with no
+ * option name: the form is an argument of the third.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -690,6 +692,42 @@ int vit_eval_update(const float* logits, int64_t ld, const int64_t* labels, int6
                     int32_t maxk, int64_t* pred /* [rows] */, int32_t* rank /* [rows] */, float* row_loss /* [rows] */,
                     int64_t* counts /* [2 + maxk] */, double* loss_sum /* [1] */,
                     int64_t* confusion /* [classes * classes] or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Attention rollout (purely added entry points, ABI 18): the attention map of one token (Abnar & Zuidema 2020)
+ * without the [B][H][T][T] probabilities of vit_attn_fwd's `probs` in memory.  The reference keeps those tensors as
+ * `.attention_probs` (transformer.py:26) and its README names "analyzing model attention maps" as a use of them; the
+ * rollout of a token is a [T] vector per image, formed as a vector-matrix chain from the last block to the first.
+ * One call is one step of that chain for one block.  With P[h][i][j] = softmax_j(scale * q_i(h) . k_j(h)) formed from
+ * qkv[B*T][3*D] (the layout and `scale` of vit_attn_fwd):
+ *   F[i][j]  = mean, max or min over h of P[h][i][j]                     (fuse)
+ *   w[i]     = r_in[i] / (1 + sum_j F[i][j])
+ *   r_out[j] = sum_i w[i] * F[i][j] + w[j]
+ * which is r_out = r_in A for A = (F + I) with its rows re-normalised.  Starting from a one-hot r at `token` and
+ * stepping through the blocks from the last to the first leaves row `token` of A_L ... A_1.
+ * The step forms its own softmax (it takes no lse), so the map is a function of qkv alone.  bf16 products are exact;
+ * logits, exp, fusing, row and column sums are fp32; r_in and r_out are fp32 [B][T].  Two launches (a workgroup per
+ * image and 32 query rows, with its rows of F in LDS; then the sum of the row blocks' partial column sums in a fixed
+ * order): no atomics, the same bits on every run.  Nothing outside qkv, r_in, r_out and the workspace's
+ * vit_attn_rollout_workspace_bytes bytes is touched, and one image's values never reach another image's output.
+ * Forms: bf16 with hd == 64 computes S on v_mfma_f32_32x32x16_bf16 (K tiles through LDS); every other case runs VALU
+ * dot products.  vit_attn_rollout_step_form takes the choice as `form`: 0 automatic (what vit_attn_rollout_step
+ * runs), 1 the VALU form, 2 the MFMA form — for A/B runs and the per-form tests.
+ * Refused (VIT_ERR_INVALID) before any launch: a NULL among qkv, r_in, r_out, workspace; a size <= 0; T > 1024;
+ * hd > 128 or hd % 4 != 0; a dtype other than VIT_F32 / VIT_BF16; fuse outside 0..2; form outside 0..2, or 2 where the
+ * MFMA form does not apply; r_in and r_out overlapping (the caller alternates two buffers); qkv not 16-B aligned.
+ * vit_attn_rollout_workspace_bytes returns 0 for a shape that the step refuses.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define VIT_ROLLOUT_MEAN 0
+#define VIT_ROLLOUT_MAX 1
+#define VIT_ROLLOUT_MIN 2
+int64_t vit_attn_rollout_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t hd, int32_t dtype, int32_t fuse);
+int vit_attn_rollout_step(const void* qkv, const float* r_in, float* r_out, int64_t B, int64_t T, int64_t H,
+                          int64_t hd, float scale, int32_t dtype /* VIT_F32 | VIT_BF16 */, int32_t fuse,
+                          void* workspace, void* stream);
+int vit_attn_rollout_step_form(const void* qkv, const float* r_in, float* r_out, int64_t B, int64_t T, int64_t H,
+                               int64_t hd, float scale, int32_t dtype, int32_t fuse, int32_t form, void* workspace,
+                               void* stream);
 
 #ifdef __cplusplus
 }

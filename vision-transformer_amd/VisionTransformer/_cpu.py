@@ -78,8 +78,12 @@ def block(blk, x, training, want_probs=False, drop_path_rate=0.0):
     return x + drop_path(F.dropout(F.linear(h, fc2.weight, fc2.bias), DROPOUT_P, training), drop_path_rate, training)
 
 
-def vit_forward(model, x):
-    """VisionTransformer.forward (vit.py:77-80) on the host: embeddings -> L blocks -> classifier on token 0."""
+def vit_forward(model, x, training=None, want_probs=None):
+    """VisionTransformer.forward (vit.py:77-80) on the host: embeddings -> L blocks -> classifier on token 0.
+    `training` / `want_probs` other than None override model.training / model.wants_attention_probs for this call
+    (VisionTransformer.attention_rollout: an eval forward that stores the probabilities, whatever the flags say)."""
+    training = model.training if training is None else training
+    want_probs = model.wants_attention_probs(x.shape[0]) if want_probs is None else want_probs
     emb = model.emdeddings
     conv = emb.sequence[0]
     if x.shape[0] != emb.cls_tkn_embd.shape[0]:
@@ -88,7 +92,7 @@ def vit_forward(model, x):
     e = patch_embed(x, conv.weight, conv.bias, emb.cls_tkn_embd, emb.pos_embd, conv.kernel_size[0])
     rates = model.drop_path_rates
     for l, blk in enumerate(model.transformer_encoder.blocks):
-        e = block(blk, e, model.training, model.wants_attention_probs(x.shape[0]), rates[l])
+        e = block(blk, e, training, want_probs, rates[l])
     fc0, _, ln, fc3 = model.mlp
     z = F.gelu(F.linear(e[:, 0, :], fc0.weight, fc0.bias))                  # token 0 = first PATCH (vit.py:80)
     z = F.layer_norm(z, (z.shape[-1],), ln.weight, ln.bias, LN_EPS)

@@ -66,6 +66,7 @@ register_optimizer_step_post_hook(_after_optimizer_step)
 
 DROPOUT_P = 0.2          # transformer.py:35,53 (config.dropout is stored but unused by the reference)
 LN_EPS = 1e-5
+PROBS_SCRATCH_BYTES = 64 << 20   # Engine._attn_fwd_as_stored: probabilities of a few images at a time, then dropped
 ALIGN = 64               # elements; every sub-tensor of the flat buffers starts 256-B aligned
 
 
@@ -533,7 +534,13 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------
     # forward
     # ------------------------------------------------------------------------------------------------------------
-    def forward(self, x, training, save, want_probs=False):
+    def forward(self, x, training, save, want_probs=False, keep_qkv=False):
+        """(logits, tape).  `keep_qkv`: (logits, tape, qkvs) with every block's qkv [B*T, 3D], first block to last
+        (rollout()'s input).  Such a forward runs as a probability-storing one does — one chain, every block's full
+        QKV GEMM and full attention, the pruned block's too — so its logits are bitwise that forward's.
+        keep_qkv="fast" differs in one thing: the attention is the kernel a plain forward runs (MFMA in bf16 at hd 64,
+        5.6x faster end to end at ViT-B/16 B 256), so the logits and the later blocks' qkv are another valid bf16
+        evaluation — a plain forward's kernels — and not the probability-storing forward's bits."""
         if not x.is_cuda:
             raise RuntimeError("VisionTransformer (HIP path) needs the input on a ROCm device; there is no CPU path")
         if x.dim() != 4 or x.shape[1] != self.C or x.shape[2] % self.P or x.shape[3] % self.P:
@@ -573,7 +580,8 @@ class Engine:
         nc = self.fwd_streams
         cols = torch.empty(B * self.N, self.CPP, dtype=dt, device=x.device)
         xcur = torch.empty(B * T, D, dtype=dt, device=x.device)
-        if (nc > 1 and not want_probs and self.profile_hook is None and B % (4 * nc) == 0
+        qkvs = []
+        if (nc > 1 and not want_probs and not keep_qkv and self.profile_hook is None and B % (4 * nc) == 0
                 and ((B // nc) * T) % 4 == 0):
             xcur = self._forward_blocks_split(x, cols, xcur, B, training, seed, save, prune, blocks, nc,
                                               paths=paths)
@@ -581,7 +589,9 @@ class Engine:
             self._embed(x, cols, xcur, 0, B)
             for l in range(L):
                 xcur, saved = self.block_forward(l, xcur, B, training, seed, save, want_probs,
-                                                 pr=prune and l == L - 1, path_scale=paths[l])
+                                                 pr=prune and l == L - 1, path_scale=paths[l], keep_qkv=keep_qkv)
+                if keep_qkv:
+                    qkvs.append(saved.qkv)
                 if save:
                     blocks.append(saved)
         # classifier on token 0 (= first PATCH, vit.py:80): Linear -> GELU(erf) -> LayerNorm(4D) -> Linear, fp32
@@ -598,11 +608,11 @@ class Engine:
             tape.seed, tape.training, tape.pruned = seed, training, prune
             # which attention the pruned block's forward ran (query 0 alone, or the full kernels): its backward must
             # be the matching one whatever row0_attention says by then (the row-0 forward writes only rows b*T)
-            tape.row0 = prune and self.row0_attention and not want_probs
+            tape.row0 = prune and self.row0_attention and not want_probs and not keep_qkv
             # ... and the drop-path rates its keep bits were drawn with: the backward's scalars follow the forward,
             # whatever model.drop_path_rates says by then
             tape.path_rates = rates if path is not None else None
-        return logits, tape
+        return (logits, tape, qkvs) if keep_qkv else (logits, tape)
 
     def _block_bufs(self, x_in, B, training, save, pr=False, q0only=False):
         """Every tensor the forward of one block writes for the B images of x_in: (BlockActs, x_out).  The only place
@@ -724,7 +734,7 @@ class Engine:
         return xcur
 
     def block_forward(self, l, x_in, B, training, seed, save, want_probs=False, *, pr=False, out=None, row0=0,
-                      attn_wgs=0, path_scale=None):
+                      attn_wgs=0, path_scale=None, keep_qkv=False):
         """Block l (transformer.py:76-79) on x_in [B*T, D] (compute dtype): x_mid = x_in + drop(MHA(ln1(x_in))),
         x_out = x_mid + drop(FFN(ln2(x_mid))).  `pr`: the post-attention part on the B token-0 rows only (the pruned
         last block).  Returns (x_out, saved): `saved` is the BlockActs block_backward needs (None unless `save`).
@@ -732,13 +742,15 @@ class Engine:
         ones — a row range (BlockActs.images) of the whole batch's, x_in being its row `row0`: the dropout bits are
         drawn at the whole batch's indices.  `path_scale` (drop path): this block's [2, rows] slice of the whole
         batch's factor table (_ops.drop_path_rows), site 0 for the attention branch and 1 for the FFN's, read at the
-        dropout's row indices; None: no drop path."""
-        q0only = pr and self.row0_attention and not want_probs  # the pruned block's attention on query 0 alone
+        dropout's row indices; None: no drop path.  `keep_qkv` (forward): the block as a probability-storing forward
+        runs it, and `saved` is returned without `save` too."""
+        # the pruned block's attention on query 0 alone
+        q0only = pr and self.row0_attention and not want_probs and not keep_qkv
         a, x_out = out if out is not None else self._block_bufs(x_in, B, training, save, pr, q0only)
         self._ln1_qkv(l, a.x_in, a.a1, a.m1, a.r1, a.qkv, q0only)
         self._attend_ffn(l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0, attn_wgs,
-                         path_scale=path_scale)
-        return x_out, a if save else None
+                         path_scale=path_scale, keep_qkv=keep_qkv)
+        return x_out, a if save or keep_qkv else None
 
     def _ln1_qkv(self, l, x_in, a1, m1, r1, qkv, kv_only):
         """The part of block l before its attention that is whole-row work: a1 = ln1(x_in), then qkv = a1 Wqkv^T —
@@ -761,8 +773,53 @@ class Engine:
             _ops.gemm(a1, wq, qkv, M, 3 * D, D, D, D, 3 * D)
         mk("gemm_fwd", 1)
 
+    def _attn_fwd_as_stored(self, a, B):
+        """keep_qkv's attention: the kernel of a probability-storing forward, hence that forward's bits in a.o,
+        without its [B, H, T, T] tensor.  vit_attn_fwd chooses by `probs` between the MFMA and the probability-writing
+        kernel where both exist (bf16 at hd 64); there the images go through a few at a time — (image, head) items are
+        independent, so the bits are the whole batch's — with their probabilities in one scratch of at most
+        PROBS_SCRATCH_BYTES.  Everywhere else the one kernel there is runs, with no probabilities at all."""
+        T, H, hd = self.T, self.H, self.hd
+        if not (self.dtype == torch.bfloat16 and hd == 64):
+            _ops.attn_fwd(a.qkv, B, T, H, hd, self.scale, o=a.o, lse=a.lse, o32=a.o32)
+            return
+        n = max(1, min(B, PROBS_SCRATCH_BYTES // (H * T * T * 4)))
+        scratch = torch.empty(n, H, T, T, dtype=torch.float32, device=a.qkv.device)
+        for b0 in range(0, B, n):
+            nb = min(n, B - b0)
+            rows = slice(b0 * T, (b0 + nb) * T)
+            _ops.attn_fwd(a.qkv[rows], nb, T, H, hd, self.scale, o=a.o[rows], lse=a.lse[b0:b0 + nb], probs=scratch,
+                          o32=None if a.o32 is None else a.o32[rows])
+
+    def rollout(self, qkvs, token=0, fuse="mean", trace=False):
+        """Attention rollout of `token` from a keep_qkv forward's qkvs: [B, T] fp32 — row `token` of A_L ... A_1 with
+        A_l = the head-fused attention of block l plus the identity, rows re-normalised (vit_hip.h "Attention
+        rollout").  One vit_attn_rollout_step per block, last block first, on the current stream with no host sync;
+        two [B, T] vectors alternate over one workspace.  `trace`: also [L, B, T], entry l the vector after block
+        l's step (entry 0 is the map)."""
+        T, H, hd, L = self.T, self.H, self.hd, self.L
+        if len(qkvs) != L:
+            raise ValueError(f"rollout: {len(qkvs)} qkv tensors for {L} blocks")
+        if not 0 <= int(token) < T:
+            raise ValueError(f"rollout: token {token} outside [0, {T})")
+        if fuse not in _ops.ROLLOUT_FUSE:
+            raise ValueError(f"rollout: head fusion {fuse!r} is not one of {sorted(_ops.ROLLOUT_FUSE)}")
+        code = _ops.ROLLOUT_FUSE[fuse]
+        dev = qkvs[0].device
+        B = qkvs[0].shape[0] // T
+        need = _ops.attn_rollout_workspace_bytes(B, T, H, hd, qkvs[0].dtype, code)
+        ws = torch.empty(max(need // 4, 1), dtype=torch.float32, device=dev)
+        steps = torch.empty(L, B, T, dtype=torch.float32, device=dev) if trace else None
+        pair = [torch.zeros(B, T, dtype=torch.float32, device=dev), torch.empty(B, T, dtype=torch.float32, device=dev)]
+        pair[0][:, int(token)] = 1.0
+        r = pair[0]
+        for l in range(L - 1, -1, -1):
+            out = steps[l] if trace else pair[1] if r is pair[0] else pair[0]
+            r = _ops.attn_rollout_step(qkvs[l], r, B, T, H, hd, self.scale, code, r_out=out, workspace=ws)
+        return (r, steps) if trace else r
+
     def _attend_ffn(self, l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0=0, attn_wgs=0, *,
-                    path_scale=None):
+                    path_scale=None, keep_qkv=False):
         """The rest of block l's forward from _ln1_qkv's a.a1 / a.qkv: attention, proj + residual, ln2, FFN +
         residual into x_out (arguments as block_forward's); returns x_out."""
         D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
@@ -787,6 +844,8 @@ class Engine:
             mk("attn_fwd", 0, 4.0 * B * H * T * hd, 2 * M * D * es + 2 * B * D * es + 4 * B * H)
             _ops.attn_fwd_row0(a.qkv, B, T, H, hd, self.scale, o=a.o, lse=a.lse)
             mk("attn_fwd", 1)
+        elif keep_qkv and keep_qkv != "fast" and not want_probs:
+            self._attn_fwd_as_stored(a, B)
         else:
             # a.o32 (training forward in bf16 with the tiled T > 256 backward): also keep O unrounded for its exact
             # delta; the fused T <= 256 backward forms delta from P and dP itself (vit_hip.h)

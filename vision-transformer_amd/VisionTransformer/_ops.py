@@ -263,6 +263,41 @@ def attn_bwd_row0(qkv, d_o0, ldo, dqkv, B, T, H, hd, scale, stream=None):
     return dqkv
 
 
+ROLLOUT_FUSE = {"mean": _lib.ROLLOUT_MEAN, "max": _lib.ROLLOUT_MAX, "min": _lib.ROLLOUT_MIN}
+
+
+def attn_rollout_workspace_bytes(B, T, H, hd, dtype, fuse):
+    return _lib.load().vit_attn_rollout_workspace_bytes(B, T, H, hd, dtype_code(dtype), fuse)
+
+
+def attn_rollout_step(qkv, r_in, B, T, H, hd, scale, fuse, r_out=None, workspace=None, form=_lib.ROLLOUT_FORM_AUTO,
+                      stream=None):
+    """One step of the attention-rollout chain (vit_attn_rollout_step): r_out[B][T] (fp32) from r_in[B][T] (fp32) and
+    one block's qkv[B*T][3*H*hd]; `fuse` is a ROLLOUT_FUSE value.  r_out must not be r_in.  `form` other than automatic
+    goes through vit_attn_rollout_step_form (A/B runs and tests)."""
+    _need_cuda(qkv, r_in, r_out, workspace)
+    if r_in.dtype != torch.float32 or not r_in.is_contiguous() or r_in.numel() != B * T:
+        raise ValueError("attn_rollout_step: r_in must be a contiguous float32 [B, T] tensor")
+    r_out = torch.empty(B, T, dtype=torch.float32, device=qkv.device) if r_out is None else r_out
+    if r_out.dtype != torch.float32 or not r_out.is_contiguous() or r_out.numel() != B * T:
+        raise ValueError("attn_rollout_step: r_out must be a contiguous float32 [B, T] tensor")
+    if not qkv.is_contiguous() or qkv.numel() != B * T * 3 * H * hd:
+        raise ValueError("attn_rollout_step: qkv must be a contiguous [B*T, 3*H*hd] tensor")
+    need = attn_rollout_workspace_bytes(B, T, H, hd, qkv.dtype, fuse)
+    if workspace is None:
+        workspace = torch.empty(max(need // 4, 1), dtype=torch.float32, device=qkv.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"attn_rollout_step: workspace holds {workspace.numel() * workspace.element_size()} bytes, "
+                         f"the step needs {need}")
+    if form == _lib.ROLLOUT_FORM_AUTO:
+        _lib.call("vit_attn_rollout_step", _ptr(qkv), _ptr(r_in), _ptr(r_out), B, T, H, hd, scale, dtype_code(qkv),
+                  fuse, _ptr(workspace), _stream(stream))
+    else:
+        _lib.call("vit_attn_rollout_step_form", _ptr(qkv), _ptr(r_in), _ptr(r_out), B, T, H, hd, scale,
+                  dtype_code(qkv), fuse, form, _ptr(workspace), _stream(stream))
+    return r_out
+
+
 def colsum(x, rows, cols, ldx, out, beta=0.0, workspace=None, alpha=1.0, stream=None):
     need = _lib.load().vit_colsum_workspace_bytes(rows, cols)
     if workspace is None or workspace.numel() * workspace.element_size() < need:

@@ -39,6 +39,9 @@ Extra (additive) API:
     the optimizer's launch, and its `ema_weights()` swaps it in and out of this model's own buffers, shadows included
     (optim.py).  `AveragedModel` still works, with the `repack()` above.
 
+  * `model.attention_rollout(x, token=0, head_fusion="mean")` — (logits, [B, T] attention-rollout maps of the token
+    the classifier reads) without any [B, H, T, T] tensor on the device, and `model.patch_map(maps, image_hw)` to lay
+    them out as patch images (rollout.py);
   * `model.drop_path_rates` — stochastic depth: a list of one rate per encoder block, built from
     `ViTConfig(drop_path_rate=...)` by timm's linspace rule and settable (a list of `num_blocks` numbers in [0, 1)).
     In training mode each block drops each of its two residual branches per image with its rate and scales the
@@ -63,6 +66,7 @@ import torch.nn as nn
 from . import _cpu
 from . import _functional as Fh
 from . import config as _config  # noqa: F401  (reference module imports config alongside transformer)
+from . import rollout as _rollout
 from . import transformer
 from ._engine import Engine, ViTFunction
 
@@ -240,3 +244,42 @@ class VisionTransformer(nn.Module):
             return ViTFunction.apply(x, self._anchor, eng, self.training, self.wants_attention_probs(x.shape[0]))
         logits, _ = eng.forward(x, self.training, save=False, want_probs=self.wants_attention_probs(x.shape[0]))
         return logits
+
+    def attention_rollout(self, x, token=0, head_fusion="mean", return_layers=False, fast_attention=False):
+        """(logits, maps [B, T] fp32): the attention rollout of `token` (rollout.py; 0 is the token the classifier
+        reads, T - 1 the CLS token) for every image of x, from an eval-mode forward under no_grad — no dropout, no
+        drop path, whatever `model.training` says; neither it nor `store_attention_probs` is changed.  With
+        `return_layers` also [L, B, T] fp32: entry l is the chain after block l's step, entry 0 the maps.
+        On a ROCm device no [B, H, T, T] tensor exists at any time: the forward keeps each block's qkv
+        (`Engine.forward(keep_qkv=True)`; its logits are bitwise those of a `store_attention_probs = True` forward) and
+        `Engine.rollout` forms the chain from them, one HIP launch pair per block, with no host sync.  A model on the
+        CPU stores the probabilities and goes through `rollout.rollout_from_probs`.  `head_fusion`: "mean", "max" or
+        "min" over the heads.  `fast_attention` (device only): the forward runs the attention kernel of a plain
+        forward instead of the probability-storing forward's — in bf16 at head size 64 the MFMA kernel, which makes
+        the call 5.6x faster at ViT-B/16 B 256; logits and maps are then those of a plain forward's
+        kernels: another valid bf16 evaluation of the model, no longer bitwise the probability-storing forward's."""
+        T = self.vit_config.num_patches + 1
+        token = _rollout.check_rollout_args(token, head_fusion, T)
+        with torch.no_grad():
+            if not x.is_cuda and all(not p.is_cuda for p in (self.mlp[3].weight, self.emdeddings.pos_embd)):
+                logits = _cpu.vit_forward(self, x, training=False, want_probs=True)
+                probs = [blk.multi_head.attention_probs for blk in self.transformer_encoder.blocks]
+                maps, layers = _rollout.rollout_from_probs([p.float() for p in probs], token, head_fusion, True)
+            else:
+                eng = self.hip_engine
+                logits, _, qkvs = eng.forward(x, False, save=False, keep_qkv="fast" if fast_attention else True)
+                maps, layers = eng.rollout(qkvs, token, head_fusion, trace=True) if return_layers else \
+                    (eng.rollout(qkvs, token, head_fusion), None)
+        return (logits, maps, layers) if return_layers else (logits, maps)
+
+    def patch_map(self, maps, image_hw):
+        """[B, T] token maps (attention_rollout) as [B, H / P, W / P] images of the patches: the CLS entry (index N,
+        appended last) is dropped and the N patch entries are laid out row-major, as the patch embedding flattens
+        them (vit.py:29).  `image_hw`: the (H, W) of the input images."""
+        P = self.vit_config.patch_size
+        gh, gw = int(image_hw[0]) // P, int(image_hw[1]) // P
+        N = self.vit_config.num_patches
+        if maps.dim() != 2 or maps.shape[1] != N + 1 or gh * gw != N:
+            raise ValueError(f"patch_map: maps must be [B, {N + 1}] and image_hw give {N} patches of {P} x {P}, got "
+                             f"{tuple(maps.shape)} and {gh} x {gw}")
+        return maps[:, :N].reshape(maps.shape[0], gh, gw)

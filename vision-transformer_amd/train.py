@@ -189,6 +189,35 @@ def validate(model, test_loader, topk=(1, 5), confusion=True):
     return metrics.compute()
 
 
+@torch.no_grad()
+def rollout_maps(model, test_loader, images=None, head_fusion="mean", token=0):
+    """Attention-rollout maps of the first `images` validation images (default: one batch) through
+    model.attention_rollout: {"maps": [K, H / P, W / P] float32, "pred": [K] int64, "label": [K] int64} as numpy
+    arrays.  Whole batches are run (a partial one padded as validate() pads it) and the result is cut to K; fewer when
+    the loader holds fewer."""
+    B = model.vit_config.batch_size
+    K = B if images is None else int(images)
+    if K <= 0:
+        raise ValueError(f"rollout_maps: images must be positive, got {images}")
+    maps, preds, labs, got = [], [], [], 0
+    for tensors, labels in test_loader:
+        if got >= K:
+            break
+        rows = tensors.shape[0]
+        if rows < B:
+            fill = tensors[-1:].expand(B - rows, *tensors.shape[1:])
+            tensors = torch.cat([tensors, fill], 0)
+        logits, m = model.attention_rollout(tensors.to(device, non_blocking=True), token, head_fusion)
+        maps.append(model.patch_map(m, tensors.shape[2:])[:rows].float().cpu())
+        preds.append(torch.argmax(logits[:rows], dim=-1).cpu())
+        labs.append(labels.cpu().long())
+        got += rows
+    if not maps:
+        raise ValueError("rollout_maps: the test loader yielded no batch")
+    return {"maps": torch.cat(maps)[:K].numpy(), "pred": torch.cat(preds)[:K].numpy(),
+            "label": torch.cat(labs)[:K].numpy()}
+
+
 def _set_epoch(loader, epoch):
     """DistributedSampler.set_epoch on the loader's sampler (also behind data.DeviceBatches), so each epoch draws a
     new shard order on every rank."""
@@ -446,9 +475,11 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     return running_loss
 
 
-def eval_only(configs, test_loader, checkpoint_dir, topk=(1, 5), confusion=True, ema=False):
+def eval_only(configs, test_loader, checkpoint_dir, topk=(1, 5), confusion=True, ema=False, rollout=None):
     """validate() once on the newest checkpoint of `checkpoint_dir` (its "ema_state_dict" with `ema`): the compute()
-    dict with the checkpoint's epoch as "epoch".  Raises FileNotFoundError when the directory holds no checkpoint."""
+    dict with the checkpoint's epoch as "epoch".  Raises FileNotFoundError when the directory holds no checkpoint.
+    `rollout`: a dict of rollout_maps() keywords plus "out"; rank 0 then writes that function's arrays to the .npz
+    file `out` after the validation pass."""
     saved_epoch = search_checkpoint(checkpoint_dir)
     if saved_epoch is None:
         raise FileNotFoundError(f"no checkpoint (N.pt) in {checkpoint_dir!r} to evaluate")
@@ -462,6 +493,10 @@ def eval_only(configs, test_loader, checkpoint_dir, topk=(1, 5), confusion=True,
     model = model.to(device)
     result = validate(model, test_loader, topk=topk, confusion=confusion)
     result["epoch"] = saved_epoch
+    if rollout is not None and _rank_world()[0] == 0:
+        import numpy as np
+        kw = dict(rollout)
+        np.savez(kw.pop("out"), **rollout_maps(model, test_loader, **kw))
     return result
 
 
@@ -582,6 +617,16 @@ def main():
     ap.add_argument("--eval-only", action="store_true",
                     help="load the newest checkpoint of --checkpoint-dir (its EMA weights with --ema-decay), validate "
                          "once, print the metrics as one JSON line and exit")
+    ap.add_argument("--rollout-out", default=None, metavar="FILE.npz",
+                    help="with --eval-only: after the validation pass write the attention-rollout maps of the first "
+                         "validation images (maps [K, H/P, W/P] float32, pred [K], label [K]) to this .npz file")
+    ap.add_argument("--rollout-images", type=int, default=None, metavar="K",
+                    help="with --rollout-out: how many images (default: one batch)")
+    ap.add_argument("--rollout-fusion", default="mean", choices=["mean", "max", "min"],
+                    help="with --rollout-out: how the heads' attention is fused")
+    ap.add_argument("--rollout-token", type=int, default=0, metavar="I",
+                    help="with --rollout-out: the token whose rollout is taken (0: the one the classifier reads; the "
+                         "CLS token is the last)")
     ap.add_argument("--reference-loop", action="store_true",
                     help="the reference's loop bookkeeping exactly: validate every epoch, restart the step counter on "
                          "resume, host-summed loss (train.py:60-119)")
@@ -653,6 +698,15 @@ def main():
                     fuse_groups=args.fuse_groups)
     if args.sched is None and args.layer_decay is None and (args.warmup_steps or args.warmup_lr or args.min_lr):
         ap.error("--warmup-steps, --warmup-lr and --min-lr need --sched")
+    if args.rollout_out is not None and not args.eval_only:
+        ap.error("--rollout-out needs --eval-only")
+    if args.rollout_out is None and (args.rollout_images is not None or args.rollout_fusion != "mean"
+                                     or args.rollout_token != 0):
+        ap.error("--rollout-images, --rollout-fusion and --rollout-token need --rollout-out")
+    if args.rollout_images is not None and args.rollout_images <= 0:
+        ap.error("--rollout-images must be positive")
+    if not 0 <= args.rollout_token <= n_patches:
+        ap.error(f"--rollout-token must lie in [0, {n_patches}]")
     if args.bench:
         steps = args.steps or 30
         sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm,
@@ -707,7 +761,10 @@ def main():
         from VisionTransformer.metrics import jsonable
         try:
             result = eval_only(cfg, test_loader, args.checkpoint_dir, topk=tuple({1, *(args.val_topk or ())}),
-                               confusion=args.val_confusion, ema=args.ema_decay is not None)
+                               confusion=args.val_confusion, ema=args.ema_decay is not None,
+                               rollout=None if args.rollout_out is None else dict(
+                                   out=args.rollout_out, images=args.rollout_images,
+                                   head_fusion=args.rollout_fusion, token=args.rollout_token))
         except (FileNotFoundError, KeyError) as e:
             ap.exit(2, f"train.py --eval-only: {e}\n")
         if rank == 0:
