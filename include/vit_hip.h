@@ -84,7 +84,9 @@ const char* vit_last_error(void);
  * vit_augment_to_u8, vit_randaug_workspace_bytes and vit_randaug_to_tensor (RandAugment), with no option name of their
  * own ("augment_path" chooses the form of vit_augment_to_u8 as it does for vit_augment_to_tensor);
  * vit_attn_rollout_workspace_bytes, vit_attn_rollout_step and vit_attn_rollout_step_form (attention rollout), with no
- * option name: the form is an argument of the third.
+ * option name: the form is an argument of the third;
+ * vit_patch_keep, vit_im2col_gather, vit_gather_pos, vit_pos_grad_gather and vit_col2im_scatter (patch dropout), with
+ * no option name.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -728,6 +730,41 @@ int vit_attn_rollout_step(const void* qkv, const float* r_in, float* r_out, int6
 int vit_attn_rollout_step_form(const void* qkv, const float* r_in, float* r_out, int64_t B, int64_t T, int64_t H,
                                int64_t hd, float scale, int32_t dtype, int32_t fuse, int32_t form, void* workspace,
                                void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Patch dropout (timm's patch_drop_rate; purely added entry points, ABI 18): a training forward keeps K of the N patch
+ * tokens of every image, so every block runs on T' = K + 1 rows per image.  Tokens 0 .. N-1 are the patches and token
+ * N is CLS (appended last, vit.py:41); the classifier reads token 0.  Patch 0 and CLS are always kept; the kept
+ * patches stay in ascending order with CLS last, so token 0 stays token 0.
+ *
+ * vit_patch_keep draws the table of one forward: idx[b][j] = the patch in row j of image b (ascending, idx[b][0] = 0),
+ *   inv[b][n] = the row of patch n, or -1 where it is dropped.  The key of patch n of image b is
+ *   vit_hash_u32(site_seed(seed, 2L, 0), b * N + n) (layers 0 .. L-1 of site_seed are the element dropout's streams,
+ *   L .. 2L-1 the drop path's); patch n >= 1 is kept iff fewer than K - 1 patches m in 1 .. N-1 have a smaller
+ *   (key, m) pair, compared lexicographically: a uniform random (K-1)-subset per image.  One workgroup per image, keys
+ *   in LDS, ranks by counting, rows by a prefix sum: no atomics, no host sync, the same bytes for the same seed.
+ * vit_im2col_gather is vit_im2col where row b * K + j of cols is patch idx[b][j]; dropped patches are never read.
+ * vit_gather_pos fills posg[b * K + j][:] = pos[idx[b][j]][:] (fp32, D % 4 == 0): the residual rows with which the
+ *   embedding GEMM keeps its single rounding of acc + bias + pos (res = posg, res_rowmod = B * K, out_group = (K, K+1)).
+ * vit_pos_grad_gather: gpos[n] = beta * gpos[n] + sum over b with inv[b][n] >= 0 of dx[b * (K+1) + inv[b][n]] for n < N
+ *   and gpos[N] = beta * gpos[N] + sum over b of the CLS rows dx[b * (K+1) + K]; dx is [B * (K+1)][D] in `dtype`, gpos
+ *   fp32 [N + 1][D].  The sum runs over b ascending in one thread: bitwise repeatable.  beta == 0 never reads gpos.
+ * vit_col2im_scatter is vit_col2im reading row b * K + inv[b][n] of cols [B * K][C*P*P]; dropped patches get zeros.
+ * A table entry outside its range (a caller's own table) is clamped (idx) or read as dropped (inv), never addressed.
+ * Refused (VIT_ERR_INVALID) before any launch: a NULL pointer; B <= 0; N, K outside 1 <= K <= N <=
+ * VIT_PATCH_KEEP_MAX_N; L < 0; B * N >= 2^31; the image / patch / dtype conditions of vit_im2col and vit_col2im.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define VIT_PATCH_KEEP_MAX_N 4096
+int vit_patch_keep(uint32_t seed, int64_t L, int64_t B, int64_t N, int64_t K, int32_t* idx /* [B][K] */,
+                   int32_t* inv /* [B][N] */, void* stream);
+int vit_im2col_gather(const void* x, int32_t x_dtype, void* cols, int32_t dtype, const int32_t* idx, int64_t B,
+                      int64_t C, int64_t H, int64_t W, int64_t P, int64_t K, void* stream);
+int vit_gather_pos(const float* pos, const int32_t* idx, float* posg, int64_t B, int64_t N, int64_t K, int64_t D,
+                   void* stream);
+int vit_pos_grad_gather(const void* dx, int32_t dtype, const int32_t* inv, float* gpos, int64_t B, int64_t N, int64_t K,
+                        int64_t D, float beta, void* stream);
+int vit_col2im_scatter(const void* cols, int32_t dtype, const int32_t* inv, void* x, int32_t x_dtype, int64_t B,
+                       int64_t C, int64_t H, int64_t W, int64_t P, int64_t K, void* stream);
 
 #ifdef __cplusplus
 }

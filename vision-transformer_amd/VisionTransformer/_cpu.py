@@ -15,8 +15,12 @@ It is written for the host's cores rather than mirrored from the reference's mod
     `model.wants_attention_probs(B)` (store_attention_probs, auto by size; [B, H, T, T] fp32 per block).
 Standard autograd throughout, so requires_grad, hooks and torch DDP (gloo) behave as for any nn.Module.
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
+
+from . import config as _config
+from ._engine import site_seed
 
 DROPOUT_P = 0.2          # transformer.py:35,53 (config.dropout is stored but unused by the reference)
 LN_EPS = 1e-5
@@ -63,6 +67,51 @@ def drop_path(y, p, training):
     return (y / (1.0 - p)) * keep.to(y.dtype)
 
 
+def patch_keep_table(seed, L, B, N, K):
+    """Host twin of vit_patch_keep (vit_hip.h "Patch dropout"): (idx int32 [B, K], inv int32 [B, N]) for the forward
+    seed `seed` (after dropout_seed) of a model with L blocks.  Key of patch n of image b: vit_hash_u32(site_seed(seed,
+    2L, 0), b * N + n); patch 0 is kept, and patch n >= 1 iff fewer than K - 1 patches of 1 .. N-1 have a smaller
+    (key, n) pair.  idx is ascending; inv[b, n] is the row of patch n or -1."""
+    if not 1 <= K <= N:
+        raise ValueError(f"patch_keep_table: need 1 <= K <= N, got K={K} N={N}")
+    ps = np.uint64(site_seed(seed, 2 * L, 0))
+    m32 = np.uint64(0xFFFFFFFF)
+    ctr = (np.arange(B * N, dtype=np.uint64) & m32).reshape(B, N)
+    x = (ctr * np.uint64(0x9E3779B1) + ps) & m32                    # the package's host hash (_engine._hash_u32),
+    x ^= x >> np.uint64(16)                                         # over a whole table at once
+    x = (x * np.uint64(0x85EBCA6B)) & m32
+    x ^= x >> np.uint64(13)
+    x = (x * np.uint64(0xC2B2AE35)) & m32
+    x ^= x >> np.uint64(16)
+    pair = (x << np.uint64(32)) | np.arange(N, dtype=np.uint64)[None, :]      # (key, n), compared as one number
+    keep = np.zeros((B, N), dtype=bool)
+    keep[:, 0] = True
+    if K > 1:
+        order = np.argsort(pair[:, 1:], axis=1, kind="stable")[:, :K - 1] + 1
+        np.put_along_axis(keep, order, True, axis=1)
+    idx = np.nonzero(keep)[1].reshape(B, K).astype(np.int32)
+    inv = np.where(keep, np.cumsum(keep, axis=1) - 1, -1).astype(np.int32)
+    return torch.from_numpy(idx), torch.from_numpy(inv)
+
+
+def check_keep_indices(keep, B, N):
+    """A caller's keep table: int32 / int64 [B, K] with 1 <= K <= N (shape and dtype only: the entries — ascending,
+    column 0 equal to 0 — are the caller's responsibility, so that a device table is never synchronised on).
+    Returns K."""
+    if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.int32, torch.int64):
+        raise TypeError("keep_indices must be an int32 or int64 tensor")
+    if keep.dim() != 2 or keep.shape[0] != B or not 1 <= keep.shape[1] <= N:
+        raise ValueError(f"keep_indices must be [B, K] = [{B}, 1..{N}], got {tuple(keep.shape)}")
+    return keep.shape[1]
+
+
+def gather_tokens(e, idx):
+    """The kept tokens of e [B, N + 1, D]: patches idx [B, K] in their order, then the CLS token (row N) — [B, K+1, D]."""
+    B, T, D = e.shape
+    rows = torch.cat([idx.to(torch.int64), torch.full((B, 1), T - 1, dtype=torch.int64, device=idx.device)], dim=1)
+    return e.gather(1, rows[:, :, None].expand(-1, -1, D))
+
+
 def block(blk, x, training, want_probs=False, drop_path_rate=0.0):
     """Pre-LN block (transformer.py:76-79): x + drop(proj(MHA(ln1 x))), then x + drop(FFN(ln2 x)); each branch
     under drop_path(., drop_path_rate)."""
@@ -78,10 +127,13 @@ def block(blk, x, training, want_probs=False, drop_path_rate=0.0):
     return x + drop_path(F.dropout(F.linear(h, fc2.weight, fc2.bias), DROPOUT_P, training), drop_path_rate, training)
 
 
-def vit_forward(model, x, training=None, want_probs=None):
+def vit_forward(model, x, training=None, want_probs=None, keep_indices=None):
     """VisionTransformer.forward (vit.py:77-80) on the host: embeddings -> L blocks -> classifier on token 0.
     `training` / `want_probs` other than None override model.training / model.wants_attention_probs for this call
-    (VisionTransformer.attention_rollout: an eval forward that stores the probabilities, whatever the flags say)."""
+    (VisionTransformer.attention_rollout: an eval forward that stores the probabilities, whatever the flags say).
+    Patch dropout (training, model.patch_drop_rate > 0 or `keep_indices`): after + pos the blocks get the kept tokens
+    alone; the table is patch_keep_table's under one seed drawn from the CPU RNG, as the device forward draws it —
+    at rate 0 nothing is drawn, so the RNG stream is the one it always was."""
     training = model.training if training is None else training
     want_probs = model.wants_attention_probs(x.shape[0]) if want_probs is None else want_probs
     emb = model.emdeddings
@@ -90,6 +142,21 @@ def vit_forward(model, x, training=None, want_probs=None):
         raise RuntimeError(f"batch size {x.shape[0]} != config.batch_size {emb.cls_tkn_embd.shape[0]} "
                            "(the CLS token parameter is batch-shaped)")
     e = patch_embed(x, conv.weight, conv.bias, emb.cls_tkn_embd, emb.pos_embd, conv.kernel_size[0])
+    B, N = e.shape[0], e.shape[1] - 1
+    rate = model.patch_drop_rate if training else 0.0
+    if keep_indices is not None:
+        if not training:
+            raise ValueError("keep_indices: patch dropout is training-only (the model is in eval mode)")
+        check_keep_indices(keep_indices, B, N)
+        idx = keep_indices.to(torch.int32)
+    elif rate > 0.0:
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        idx = patch_keep_table(seed, len(model.transformer_encoder.blocks), B, N, _config.patch_keep_count(N, rate))[0]
+    else:
+        idx = None
+    if idx is not None:
+        e = gather_tokens(e, idx)
+        model.last_patch_keep = idx
     rates = model.drop_path_rates
     for l, blk in enumerate(model.transformer_encoder.blocks):
         e = block(blk, e, training, want_probs, rates[l])

@@ -30,6 +30,7 @@ from torch.optim.optimizer import register_optimizer_step_post_hook
 from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib, _ops
+from . import config as _config
 from ._ops import ACT_NONE, ACT_RELU
 
 # parameter -> its compute-dtype shadow view (refreshed by FusedAdamW's kernel).  Kept beside the parameters, not as
@@ -145,7 +146,7 @@ def head_split_for(m, n, k):
 class Tape:
     """Activations saved by a training forward (`blocks`: one BlockActs per encoder block)."""
     __slots__ = ("B", "cols", "blocks", "z", "u", "gz", "zn", "mh", "rh", "seed", "training", "x_shape", "x_dtype",
-                 "x_grad", "pruned", "row0", "path_rates")
+                 "x_grad", "pruned", "row0", "path_rates", "T", "K", "idx", "inv")
 
 
 # per-block gradient regions, in their order in the flat gradient buffer (qkv_w: the fused [3D, D] matrix of every head)
@@ -223,7 +224,7 @@ class Engine:
         self._tok = None
         self._ptr_sig = None
         self._ver_sig = None
-        self.stats = {"packs": 0}
+        self.stats = {"packs": 0, "split_forwards": 0}      # repacks; forwards that ran as chains on several streams
         # callable(family, phase, flop, nbytes) around the hot launches (bench.py's live HIP-event roofline):
         # phase 0 before the launch with its algorithmic FLOPs / HBM bytes, phase 1 after it, same stream
         self.profile_hook = None
@@ -534,8 +535,12 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------
     # forward
     # ------------------------------------------------------------------------------------------------------------
-    def forward(self, x, training, save, want_probs=False, keep_qkv=False):
-        """(logits, tape).  `keep_qkv`: (logits, tape, qkvs) with every block's qkv [B*T, 3D], first block to last
+    def forward(self, x, training, save, want_probs=False, keep_qkv=False, keep=None):
+        """(logits, tape).  Patch dropout (a training forward with model.patch_drop_rate > 0, or `keep`: the caller's
+        own table, int32 / int64 [B, K] on the device, ascending, column 0 equal to 0, checked for shape and dtype only):
+        the embedding computes the kept patches alone and every block runs on T' = K + 1 tokens per image; the tape
+        records T', K and the table, which is all the backward reads.
+        `keep_qkv`: (logits, tape, qkvs) with every block's qkv [B*T, 3D], first block to last
         (rollout()'s input).  Such a forward runs as a probability-storing one does — one chain, every block's full
         QKV GEMM and full attention, the pruned block's too — so its logits are bitwise that forward's.
         keep_qkv="fast" differs in one thing: the attention is the kernel a plain forward runs (MFMA in bf16 at hd 64,
@@ -558,10 +563,35 @@ class Engine:
         x = x.contiguous()
         if x.dtype not in (torch.float32, torch.bfloat16):
             x = x.float()
-        D, T, L, dt = self.D, self.T, self.L, self.dtype
+        D, N, L, dt = self.D, self.N, self.L, self.dtype
         prm = self.params
         seed = dropout_seed(int(torch.randint(0, 2 ** 31 - 1, (1,)).item()), self.dropout_rank) if training else 0
         tape = Tape() if save else None
+        # Patch dropout: the table of this forward (idx [B, K]: the kept patches, ascending; inv [B, N]: a patch's row
+        # or -1), drawn on the stream from the forward's seed with no host sync, or the caller's.  Without one (eval,
+        # rate 0) T and K are the model's and every launch is the one it always was.
+        rate = self.model_ref().patch_drop_rate if training else 0.0
+        idx = inv = posg = None
+        if keep is not None:
+            if not training:
+                raise ValueError("keep: patch dropout is training-only (the model is in eval mode)")
+            if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.int32, torch.int64):
+                raise TypeError("keep must be an int32 or int64 tensor")
+            if keep.dim() != 2 or keep.shape[0] != B or not 1 <= keep.shape[1] <= N or keep.device != x.device:
+                raise ValueError(f"keep must be [B, K] = [{B}, 1..{N}] on {x.device}, got {tuple(keep.shape)} on "
+                                 f"{keep.device}")
+            idx = keep.clamp(0, N - 1).to(torch.int32).contiguous()
+            inv = torch.full((B, N), -1, dtype=torch.int32, device=x.device)
+            inv.scatter_(1, idx.long(), torch.arange(idx.shape[1], dtype=torch.int32, device=x.device).expand(B, -1))
+        elif rate > 0.0:
+            idx, inv = _ops.patch_keep(seed, L, B, N, _config.patch_keep_count(N, rate), x.device)
+        K = N if idx is None else idx.shape[1]
+        T = K + 1
+        if idx is not None:
+            # the fp32 residual rows of the gathered embedding GEMM: pos of every kept patch (vit_gather_pos)
+            posg = _ops.gather_pos(prm["pos"], idx, N)
+        if training:
+            self.model_ref().last_patch_keep = idx
         # Stochastic depth (model.drop_path_rates, training only): one launch fills the per-row factor table of every
         # (block, site) — 1 / (1 - p_l) on the rows of the images that keep the branch, 0 on the others — which the
         # proj / fc2 GEMMs of the blocks with p_l > 0 apply in their epilogue (vit_gemm_rowscale).  All rates 0: no
@@ -578,18 +608,20 @@ class Engine:
         # gradients as computing all B*T rows and discarding the rest.  `prune_last = False` computes every row.
         prune = self.prune_last
         nc = self.fwd_streams
-        cols = torch.empty(B * self.N, self.CPP, dtype=dt, device=x.device)
+        cols = torch.empty(B * K, self.CPP, dtype=dt, device=x.device)
         xcur = torch.empty(B * T, D, dtype=dt, device=x.device)
         qkvs = []
         if (nc > 1 and not want_probs and not keep_qkv and self.profile_hook is None and B % (4 * nc) == 0
                 and ((B // nc) * T) % 4 == 0):
+            self.stats["split_forwards"] += 1
             xcur = self._forward_blocks_split(x, cols, xcur, B, training, seed, save, prune, blocks, nc,
-                                              paths=paths)
+                                              paths=paths, T=T, idx=idx, posg=posg)
         else:
-            self._embed(x, cols, xcur, 0, B)
+            self._embed(x, cols, xcur, 0, B, idx, posg)
             for l in range(L):
                 xcur, saved = self.block_forward(l, xcur, B, training, seed, save, want_probs,
-                                                 pr=prune and l == L - 1, path_scale=paths[l], keep_qkv=keep_qkv)
+                                                 pr=prune and l == L - 1, path_scale=paths[l], keep_qkv=keep_qkv,
+                                                 T=T)
                 if keep_qkv:
                     qkvs.append(saved.qkv)
                 if save:
@@ -612,15 +644,19 @@ class Engine:
             # ... and the drop-path rates its keep bits were drawn with: the backward's scalars follow the forward,
             # whatever model.drop_path_rates says by then
             tape.path_rates = rates if path is not None else None
+            # ... and the token count and keep table of this forward (patch dropout; idx / inv None without one)
+            tape.T, tape.K, tape.idx, tape.inv = T, K, idx, inv
         return (logits, tape, qkvs) if keep_qkv else (logits, tape)
 
-    def _block_bufs(self, x_in, B, training, save, pr=False, q0only=False):
+    def _block_bufs(self, x_in, B, training, save, pr=False, q0only=False, T=None):
         """Every tensor the forward of one block writes for the B images of x_in: (BlockActs, x_out).  The only place
         that says which exist and how large they are.  `pr` (the pruned last block): the post-attention tensors and
         masks on the B token-0 rows; `q0only`: its attention runs on query 0 alone (no fp32 O).  The masks exist only
         where a backward will read them: hm (ReLU) on a saving forward, pm / fm (dropout keep bits) on a saving
-        training one; o32 where the attention backward at this shape takes it."""
-        D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
+        training one; o32 where the attention backward at this shape takes it.  `T`: tokens per image of this forward
+        (None: the model's N + 1)."""
+        D, H, hd, dt = self.D, self.H, self.hd, self.dtype
+        T = self.T if T is None else T
         M = B * T
         R = B if pr else M
         dev = x_in.device
@@ -635,13 +671,28 @@ class Engine:
             fm=_ops.mask4_empty(R, D, dev) if save and training else None)
         return acts, e(R, D)
 
-    def _embed(self, x, cols, xcur, b0, B):
+    def _embed(self, x, cols, xcur, b0, B, idx=None, posg=None):
         """Patch embedding (vit.py:21-29, 39-42) of images b0 .. b0+B-1 into their rows of the whole-batch cols /
         xcur: im2col, the conv as a GEMM with conv bias + pos and the (b, n) -> b*T + n row remap in its epilogue,
-        then the CLS rows (appended LAST, vit.py:41)."""
+        then the CLS rows (appended LAST, vit.py:41).  `idx` (patch dropout, the whole batch's [B, K] table, with
+        `posg` = pos of every kept patch): only the kept patches are read and embedded — the same GEMM epilogue with
+        the gathered rows as its residual, hence the same single rounding of acc + bias + pos, into T' = K + 1 rows per
+        image; the CLS rows still carry pos[N]."""
         D, T, N, dt = self.D, self.T, self.N, self.dtype
         es = 2 if dt == torch.bfloat16 else 4
         prm = self.params
+        if idx is not None:
+            K = idx.shape[1]
+            cl = cols[b0 * K:(b0 + B) * K]
+            xc = xcur[b0 * (K + 1):(b0 + B) * (K + 1)]
+            _ops.im2col_gather(x[b0:b0 + B], self.P, dt, idx[b0:b0 + B], cols=cl)
+            self._mark("gemm_fwd", 0, 2.0 * B * K * D * self.CPP, (B * K + D) * self.CPP * es + B * K * D * (es + 4))
+            _ops.gemm(cl, self.ww["conv_w"], xc, B * K, D, self.CPP, self.CPP, self.CPP, D, bias=prm["conv_b"],
+                      res=posg[b0 * K:(b0 + B) * K], ldres=D, res_rowmod=B * K, out_group=(K, K + 1))
+            self._mark("gemm_fwd", 1)
+            # vit_embed_cls adds row T' - 1 of the table it is given: handed pos from row N - K on, that is pos[N]
+            _ops.embed_cls(prm["cls"].reshape(-1, D)[b0:b0 + B], prm["pos"].view(T, D)[N - K:], xc, B, K + 1, D)
+            return
         cl = cols[b0 * N:(b0 + B) * N]
         xc = xcur[b0 * T:(b0 + B) * T]
         _ops.im2col(x[b0:b0 + B], self.P, dt, cols=cl)                                # vit.py:21-29 as GEMM
@@ -651,16 +702,19 @@ class Engine:
         self._mark("gemm_fwd", 1)
         _ops.embed_cls(prm["cls"].reshape(-1, D)[b0:b0 + B], prm["pos"], xc, B, T, D)  # CLS appended LAST
 
-    def _forward_blocks_split(self, x, cols, xcur, B, training, seed, save, prune, blocks, nc=2, *, paths=None):
+    def _forward_blocks_split(self, x, cols, xcur, B, training, seed, save, prune, blocks, nc=2, *, paths=None,
+                              T=None, idx=None, posg=None):
         """The patch embedding and the encoder blocks as nc chains of B/nc images on nc HIP streams (default two),
         into the whole-batch cols / xcur allocated on the current stream, up to the last block's output, which the
         current stream then waits for.  Every kernel is the one-chain forward's on a row range (rows are
         independent; dropout indices are the whole batch's), so the outputs are bitwise the same; the chains fill
         each other's idle CUs.  The blocks' outputs are whole-batch buffers allocated on the current stream and
         recorded on every chain stream.  `paths`: per block, its slice of the drop-path factor table (forward) or
-        None; a chain's GEMMs read the whole batch's slice at their rows."""
+        None; a chain's GEMMs read the whole batch's slice at their rows.  `T`: tokens per image of this forward (None:
+        the model's); `idx` / `posg` (patch dropout): the whole batch's keep table and gathered pos rows, of which
+        each chain's embedding takes its images'."""
         paths = paths if paths is not None else [None] * self.L
-        T, L = self.T, self.L
+        T, L = self.T if T is None else T, self.L
         dev = xcur.device
         cur = torch.cuda.current_stream(dev)
         if self._fwd_pair is None or len(self._fwd_pair) != nc or self._fwd_pair[0].device != dev:
@@ -676,10 +730,10 @@ class Engine:
                     for st in streams:
                         t.record_stream(st)
 
-        on_chains((x, cols, xcur, *paths))         # (views of one table: each records its storage)
+        on_chains((x, cols, xcur, idx, posg, *paths))         # (views of one table: each records its storage)
         for i, st in enumerate(streams):
             with torch.cuda.stream(st):
-                self._embed(x, cols, xcur, i * Bh, Bh)
+                self._embed(x, cols, xcur, i * Bh, Bh, idx, posg)
         # the ring attention forward of one chain on 3/4 of the CUs, so the other chain's GEMMs run beside it instead
         # of waiting for the whole latency-bound kernel (one box, interleaved: 30.50 -> 30.19 ms/step; 1/2 and 7/8 of
         # the CUs gain less) — unless the caller set the attn_fwd_grid option itself.  Passed per call (vit_attn_fwd's
@@ -694,12 +748,12 @@ class Engine:
         # reads and writes only its own rows, in order on its own stream, so block l + 2 may overwrite block l's rows
         # of a chain once that chain's block l + 1 consumed them (fresh sets per block, each recorded on
         # both streams, let the caching allocator hold up to L blocks of activations while the host runs ahead)
-        ping = None if save else [self._block_bufs(xcur, B, training, save) for _ in range(2)]
+        ping = None if save else [self._block_bufs(xcur, B, training, save, T=T) for _ in range(2)]
         for acts, x_out in ping or ():
             on_chains((*acts, x_out))
         for l in range(nsplit):
             if save:
-                acts, x_out = self._block_bufs(xcur, B, training, save)
+                acts, x_out = self._block_bufs(xcur, B, training, save, T=T)
                 on_chains((*acts, x_out))
             else:
                 acts, x_out = ping[l % 2]
@@ -708,13 +762,13 @@ class Engine:
                 with torch.cuda.stream(st):
                     part = acts.images(i * Bh, Bh, T)
                     self.block_forward(l, part.x_in, Bh, training, seed, save, out=(part, x_out[i * Mh:(i + 1) * Mh]),
-                                       row0=i * Mh, attn_wgs=wgs, path_scale=paths[l])
+                                       row0=i * Mh, attn_wgs=wgs, path_scale=paths[l], T=T)
             if save:
                 blocks.append(acts)
             xcur = x_out
         if nsplit < L:
             q0only = self.row0_attention
-            acts, x_out = self._block_bufs(xcur, B, training, save, True, q0only)
+            acts, x_out = self._block_bufs(xcur, B, training, save, True, q0only, T)
             whole = (acts.x_in, acts.a1, acts.m1, acts.r1, acts.qkv)
             if q0only:
                 # the pruned block's ln1 and K / V GEMM are whole-row work: per chain too
@@ -728,13 +782,13 @@ class Engine:
             if not q0only:
                 self._ln1_qkv(L - 1, *whole, False)
             xcur = self._attend_ffn(L - 1, acts, x_out, B, training, seed, save, False, True, q0only,
-                                    path_scale=paths[L - 1])
+                                    path_scale=paths[L - 1], T=T)
             if save:
                 blocks.append(acts)
         return xcur
 
     def block_forward(self, l, x_in, B, training, seed, save, want_probs=False, *, pr=False, out=None, row0=0,
-                      attn_wgs=0, path_scale=None, keep_qkv=False):
+                      attn_wgs=0, path_scale=None, keep_qkv=False, T=None):
         """Block l (transformer.py:76-79) on x_in [B*T, D] (compute dtype): x_mid = x_in + drop(MHA(ln1(x_in))),
         x_out = x_mid + drop(FFN(ln2(x_mid))).  `pr`: the post-attention part on the B token-0 rows only (the pruned
         last block).  Returns (x_out, saved): `saved` is the BlockActs block_backward needs (None unless `save`).
@@ -743,13 +797,14 @@ class Engine:
         drawn at the whole batch's indices.  `path_scale` (drop path): this block's [2, rows] slice of the whole
         batch's factor table (_ops.drop_path_rows), site 0 for the attention branch and 1 for the FFN's, read at the
         dropout's row indices; None: no drop path.  `keep_qkv` (forward): the block as a probability-storing forward
-        runs it, and `saved` is returned without `save` too."""
+        runs it, and `saved` is returned without `save` too.  `T`: tokens per image of x_in (None: the model's N + 1;
+        under patch dropout the forward's K + 1)."""
         # the pruned block's attention on query 0 alone
         q0only = pr and self.row0_attention and not want_probs and not keep_qkv
-        a, x_out = out if out is not None else self._block_bufs(x_in, B, training, save, pr, q0only)
+        a, x_out = out if out is not None else self._block_bufs(x_in, B, training, save, pr, q0only, T)
         self._ln1_qkv(l, a.x_in, a.a1, a.m1, a.r1, a.qkv, q0only)
         self._attend_ffn(l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0, attn_wgs,
-                         path_scale=path_scale, keep_qkv=keep_qkv)
+                         path_scale=path_scale, keep_qkv=keep_qkv, T=T)
         return x_out, a if save or keep_qkv else None
 
     def _ln1_qkv(self, l, x_in, a1, m1, r1, qkv, kv_only):
@@ -819,10 +874,11 @@ class Engine:
         return (r, steps) if trace else r
 
     def _attend_ffn(self, l, a, x_out, B, training, seed, save, want_probs, pr, q0only, row0=0, attn_wgs=0, *,
-                    path_scale=None, keep_qkv=False):
+                    path_scale=None, keep_qkv=False, T=None):
         """The rest of block l's forward from _ln1_qkv's a.a1 / a.qkv: attention, proj + residual, ln2, FFN +
         residual into x_out (arguments as block_forward's); returns x_out."""
-        D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
+        D, H, hd, dt = self.D, self.H, self.hd, self.dtype
+        T = self.T if T is None else T
         M = B * T
         es = 2 if dt == torch.bfloat16 else 4
         prm = self.params
@@ -937,7 +993,9 @@ class Engine:
         return self._comm_events[0].elapsed_time(self._comm_events[1])
 
     def backward(self, tape, dlogits):
-        D, T, N, L, dt = self.D, self.T, self.N, self.L, self.dtype
+        D, L, dt = self.D, self.L, self.dtype
+        # tokens per image and patches kept of the forward being differentiated: the tape's, never the model's
+        T, K = tape.T, tape.K
         B = tape.B
         M = B * T
         prm, gw = self.params, self.gw
@@ -1020,30 +1078,37 @@ class Engine:
             dx, g1n = self.block_backward(l, tape.blocks[l], dx, g1, g1_summed, beta, req, side, tape.training, B,
                                           pruned and l == L - 1, chain_prev=l > 0, prev_mask=prev_mask,
                                           row0=tape.row0 and l == L - 1, path_rate=rates[l],
-                                          prev_path_rate=rates[l - 1] if l > 0 else 0.0)
+                                          prev_path_rate=rates[l - 1] if l > 0 else 0.0, T=T)
             g1_summed = l > 0
             self._bucket_ready(self.block_range[l], side)
             g1 = g1n if g1n is not None else dx
         dimg = None
         if need_from[0]:
-            # ---- embedding (vit.py:39-42): dx = d(x0) [B*T, D]
+            # ---- embedding (vit.py:39-42): dx = d(x0) [B*T, D]; K = T - 1 patch rows per image — all N patches, or
+            # under patch dropout the kept ones (tape.idx / tape.inv), whose gradients are scattered back
             if req["cls"]:
-                _ops.copy2d(dx[N:], T * D, gw["cls"].view(B, D), D, B, D, beta=beta)       # CLS row of every image
+                _ops.copy2d(dx[K:], T * D, gw["cls"].view(B, D), D, B, D, beta=beta)       # CLS row of every image
             if req["pos"]:
-                _ops.colsum(dx, B, T * D, T * D, gw["pos"].view(-1), beta=beta)            # pos: sum over the batch
-            dpatch = torch.empty(B * N, D, dtype=dt, device=dev)
-            _ops.copy2d(dx, D, dpatch, D, B * N, D, group=(N, T))
+                if tape.inv is None:
+                    _ops.colsum(dx, B, T * D, T * D, gw["pos"].view(-1), beta=beta)        # pos: sum over the batch
+                else:                         # ... over the images that kept the position (vit_pos_grad_gather)
+                    _ops.pos_grad_gather(dx, tape.inv, K, gw["pos"], beta=beta)
+            dpatch = torch.empty(B * K, D, dtype=dt, device=dev)
+            _ops.copy2d(dx, D, dpatch, D, B * K, D, group=(K, T))
             if req["conv_b"]:
-                _ops.colsum(dpatch, B * N, D, D, gw["conv_b"], beta=beta)
+                _ops.colsum(dpatch, B * K, D, D, gw["conv_b"], beta=beta)
             if req["conv_w"]:
-                self._wgrad(dpatch, tape.cols, gw["conv_w"], D, self.CPP, B * N, D, self.CPP, beta, side,
+                self._wgrad(dpatch, tape.cols, gw["conv_w"], D, self.CPP, B * K, D, self.CPP, beta, side,
                             "gemm_wgrad")
             if tape.x_grad:                   # input-image gradient: conv dgrad = dpatch W, scattered back (col2im)
-                dcols = torch.empty(B * N, self.CPP, dtype=dt, device=dev)
-                _ops.gemm(dpatch, self.ww["conv_w"], dcols, B * N, self.CPP, D, D, self.CPP, self.CPP,
+                dcols = torch.empty(B * K, self.CPP, dtype=dt, device=dev)
+                _ops.gemm(dpatch, self.ww["conv_w"], dcols, B * K, self.CPP, D, D, self.CPP, self.CPP,
                           b_kcontig=False)
                 dimg = torch.empty(tape.x_shape, dtype=tape.x_dtype, device=dev)
-                _ops.col2im(dcols, dimg, self.P)
+                if tape.inv is None:
+                    _ops.col2im(dcols, dimg, self.P)
+                else:                         # zeros under the dropped patches (vit_col2im_scatter)
+                    _ops.col2im_scatter(dcols, tape.inv, K, dimg, self.P)
         self._bucket_ready(self.embed_range, side)
         if side is not None:
             torch.cuda.current_stream(dev).wait_stream(side)      # every weight gradient is in G before the step
@@ -1052,7 +1117,7 @@ class Engine:
         return dimg
 
     def block_backward(self, l, acts, dx, g1, g1_summed, beta, req, side, training, B, pr=False, chain_prev=False,
-                       prev_mask=None, row0=None, *, path_rate=0.0, prev_path_rate=0.0):
+                       prev_mask=None, row0=None, *, path_rate=0.0, prev_path_rate=0.0, T=None):
         """Backward of block l (`acts`: its forward's BlockActs) from d(x_out) = dx and g1 = the fc2-dropout-masked dx
         (dx itself in eval).  Writes the block's weight gradients into the flat buffer (beta: 0 overwrite / 1
         accumulate; req: which regions want a gradient) and returns (dx_in, g1n).  `chain_prev`: there is a block l-1
@@ -1065,7 +1130,8 @@ class Engine:
         consumers, the masks themselves being the forward's combined keep bits."""
         if row0 is None:
             row0 = pr and self.row0_attention
-        D, T, H, hd, dt = self.D, self.T, self.H, self.hd, self.dtype
+        D, H, hd, dt = self.D, self.H, self.hd, self.dtype
+        T = self.T if T is None else T               # tokens per image of the forward (Tape.T under patch dropout)
         M = B * T
         gw = self.gw
         prm = self.params
@@ -1234,8 +1300,8 @@ class ViTFunction(torch.autograd.Function):
     """One autograd node for the whole network; gradients land in the engine's flat buffer (param.grad views)."""
 
     @staticmethod
-    def forward(ctx, x, anchor, engine, training, want_probs):
-        logits, tape = engine.forward(x, training, save=True, want_probs=want_probs)
+    def forward(ctx, x, anchor, engine, training, want_probs, keep=None):
+        logits, tape = engine.forward(x, training, save=True, want_probs=want_probs, keep=keep)
         tape.x_grad = ctx.needs_input_grad[0]
         ctx.engine = engine
         ctx.tape = tape
@@ -1248,4 +1314,4 @@ class ViTFunction(torch.autograd.Function):
         dimg = ctx.engine.backward(ctx.tape, dlogits)
         ctx.tape = None
         ctx.engine.run_param_hooks()
-        return dimg, None, None, None, None
+        return dimg, None, None, None, None, None

@@ -150,9 +150,19 @@ def head_attention(x, wq, wk, wv):
     return HeadAttentionFn.apply(x, wq, wk, wv)
 
 
-def patch_embed(x, w, b, cls, pos, P, dtype):
+def patch_embed(x, w, b, cls, pos, P, dtype, keep=None):
+    """`keep` (patch dropout, int32 / int64 [B, K]): on the host the kept tokens of the embedding (the patches of
+    `keep` in its order, then CLS).  On the device the gathering embedding lives in the fused engine only
+    (`VisionTransformer.forward(x, keep_indices=...)`, `Engine.forward(keep=...)`): the module-level op refuses it."""
     if _host(x, w, b, cls, pos):
-        return _cpu.patch_embed(x, w, b, cls, pos, P)
+        e = _cpu.patch_embed(x, w, b, cls, pos, P)
+        if keep is None:
+            return e
+        _cpu.check_keep_indices(keep, e.shape[0], e.shape[1] - 1)
+        return _cpu.gather_tokens(e, keep)
+    if keep is not None:
+        raise NotImplementedError("patch_embed(keep=...) on a ROCm device is implemented by the fused engine only: "
+                                  "call VisionTransformer.forward(x, keep_indices=keep) (Engine.forward(keep=...))")
     return PatchEmbedFn.apply(x, w, b, cls, pos, P, dtype)
 
 

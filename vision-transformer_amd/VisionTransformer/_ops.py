@@ -175,6 +175,81 @@ def embed_cls(cls, pos, x0, B, T, D, stream=None):
     _lib.call("vit_embed_cls", _ptr(cls), _ptr(pos), _ptr(x0), dtype_code(x0), B, T, D, _stream(stream))
 
 
+# ---- patch dropout (vit_hip.h "Patch dropout"): the keep table and the gathering / scattering embedding kernels
+def _check_table(t, B, n, what):
+    if t.dtype != torch.int32 or tuple(t.shape) != (B, n) or not t.is_contiguous():
+        raise TypeError(f"{what} must be a contiguous int32 [{B}, {n}] tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def patch_keep(seed, L, B, N, K, device, idx=None, inv=None, stream=None):
+    """(idx int32 [B, K], inv int32 [B, N]) of vit_patch_keep: the K kept patches of every image in ascending order
+    (column 0 is patch 0) and, per patch, its row or -1.  No host sync."""
+    idx = torch.empty(B, K, dtype=torch.int32, device=device) if idx is None else idx
+    inv = torch.empty(B, N, dtype=torch.int32, device=device) if inv is None else inv
+    _need_cuda(idx, inv)
+    _check_table(idx, B, K, "patch_keep: idx")
+    _check_table(inv, B, N, "patch_keep: inv")
+    _lib.call("vit_patch_keep", seed & 0xFFFFFFFF, L, B, N, K, _ptr(idx), _ptr(inv), _stream(stream))
+    return idx, inv
+
+
+def im2col_gather(x, P, dtype, idx, cols=None, stream=None):
+    """im2col of the patches idx [B, K] names: cols [B*K, C*P*P], row b*K + j from patch idx[b, j]."""
+    _need_cuda(x, idx)
+    B, C, H, W = x.shape
+    K = idx.shape[1]
+    _check_table(idx, B, K, "im2col_gather: idx")
+    cols = torch.empty(B * K, C * P * P, dtype=dtype, device=x.device) if cols is None else cols
+    if cols.numel() != B * K * C * P * P or not cols.is_contiguous() or not x.is_contiguous():
+        raise ValueError("im2col_gather: x must be contiguous and cols a contiguous [B*K, C*P*P]")
+    _lib.call("vit_im2col_gather", _ptr(x), dtype_code(x), _ptr(cols), dtype_code(cols), _ptr(idx), B, C, H, W, P, K,
+              _stream(stream))
+    return cols
+
+
+def gather_pos(pos, idx, N, out=None, stream=None):
+    """float32 [B*K, D]: row b*K + j = pos[idx[b, j]] (pos: float32 [>= N, D], contiguous)."""
+    _need_cuda(pos, idx)
+    B, K = idx.shape
+    D = pos.shape[-1]
+    _check_table(idx, B, K, "gather_pos: idx")
+    if pos.dtype != torch.float32 or not pos.is_contiguous() or pos.numel() < N * D:
+        raise TypeError("gather_pos: pos must be contiguous float32 with at least N rows")
+    out = torch.empty(B * K, D, dtype=torch.float32, device=pos.device) if out is None else out
+    if out.dtype != torch.float32 or out.numel() != B * K * D or not out.is_contiguous():
+        raise TypeError("gather_pos: out must be contiguous float32 [B*K, D]")
+    _lib.call("vit_gather_pos", _ptr(pos), _ptr(idx), _ptr(out), B, N, K, D, _stream(stream))
+    return out
+
+
+def pos_grad_gather(dx, inv, K, gpos, beta=0.0, stream=None):
+    """gpos [N+1, D] (float32) = beta * gpos + per position the sum of its rows of dx [B*(K+1), D] over the images that
+    kept it (inv [B, N]); position N sums the CLS rows.  Deterministic."""
+    _need_cuda(dx, inv, gpos)
+    B, N = inv.shape
+    D = dx.shape[-1]
+    _check_table(inv, B, N, "pos_grad_gather: inv")
+    if not dx.is_contiguous() or dx.numel() != B * (K + 1) * D:
+        raise ValueError("pos_grad_gather: dx must be a contiguous [B*(K+1), D]")
+    if gpos.dtype != torch.float32 or not gpos.is_contiguous() or gpos.numel() != (N + 1) * D:
+        raise TypeError("pos_grad_gather: gpos must be contiguous float32 with (N+1)*D elements")
+    _lib.call("vit_pos_grad_gather", _ptr(dx), dtype_code(dx), _ptr(inv), _ptr(gpos), B, N, K, D, float(beta),
+              _stream(stream))
+    return gpos
+
+
+def col2im_scatter(cols, inv, K, x, P, stream=None):
+    """col2im of gathered cols [B*K, C*P*P]: patch n of image b from row b*K + inv[b, n], zeros where inv < 0."""
+    _need_cuda(cols, inv, x)
+    B, C, H, W = x.shape
+    _check_table(inv, B, (H // P) * (W // P), "col2im_scatter: inv")
+    if not cols.is_contiguous() or cols.numel() != B * K * C * P * P or not x.is_contiguous():
+        raise ValueError("col2im_scatter: cols must be a contiguous [B*K, C*P*P] and x contiguous")
+    _lib.call("vit_col2im_scatter", _ptr(cols), dtype_code(cols), _ptr(inv), _ptr(x), dtype_code(x), B, C, H, W, P, K,
+              _stream(stream))
+    return x
+
+
 def layernorm_fwd(x2d, gamma, beta, y=None, eps=1e-5, stream=None, mean=None, rstd=None):
     _need_cuda(x2d, gamma, beta)
     rows, cols = x2d.shape

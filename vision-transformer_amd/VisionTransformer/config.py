@@ -10,6 +10,10 @@ Differences, all optional / additive:
   * `drop_path_rate` (new, keyword-only, default 0): stochastic depth.  Block l of L drops each of its two residual
     branches per image with rate `drop_path_rates(rate, L)[l]` — timm's linear rule, 0 for the first block, `rate`
     for the last — in training mode only; 0 is exactly the model without the keyword.
+  * `patch_drop_rate` (new, keyword-only, default 0): patch dropout (timm's patch_drop_rate).  In training mode every
+    image keeps `patch_keep_count(num_patches, rate)` of its patch tokens — patch 0, which the classifier reads, and a
+    uniform random subset of the others — plus the CLS token, and every block runs on those tokens alone; 0 and eval
+    mode are exactly the model without the keyword.
 """
 import math
 
@@ -34,6 +38,16 @@ def check_drop_path_rate(p, what="drop_path_rate"):
     return p
 
 
+def check_patch_drop_rate(p, what="patch_drop_rate"):
+    """`p` as a float in [0, 1), or ValueError / TypeError (the rule of check_drop_path_rate)."""
+    return check_drop_path_rate(p, what)
+
+
+def patch_keep_count(N, rate):
+    """Patches kept of N at patch-dropout rate `rate`: max(1, int(N * (1 - rate))), timm's rule; N at rate 0."""
+    return max(1, int(N * (1 - check_patch_drop_rate(rate))))
+
+
 def drop_path_rates(rate, num_blocks):
     """Per-block rates, timm's rule: [x.item() for x in torch.linspace(0, rate, num_blocks)]."""
     return [x.item() for x in torch.linspace(0, check_drop_path_rate(rate), num_blocks)]
@@ -41,7 +55,8 @@ def drop_path_rates(rate, num_blocks):
 
 class ViTConfig:
     def __init__(self, input_channels, num_classes, num_patches, embedding_size, patch_size, num_heads, num_blocks,
-                 device, batch_size, dropout=0.2, precision=torch.float32, *, compute_dtype=None, drop_path_rate=0.0):
+                 device, batch_size, dropout=0.2, precision=torch.float32, *, compute_dtype=None, drop_path_rate=0.0,
+                 patch_drop_rate=0.0):
         self.input_channels = input_channels
         self.num_classes = num_classes
         self.num_patches = num_patches
@@ -59,6 +74,7 @@ class ViTConfig:
             raise ValueError(f"compute_dtype must be torch.float32 or torch.bfloat16, got {compute_dtype}")
         self.compute_dtype = compute_dtype
         self.drop_path_rate = check_drop_path_rate(drop_path_rate)
+        self.patch_drop_rate = check_patch_drop_rate(patch_drop_rate)
 
     @classmethod
     def preset(cls, name, img_size=224, patch_size=16, num_classes=1000, batch_size=256, device="cuda",

@@ -47,7 +47,16 @@ Extra (additive) API:
     In training mode each block drops each of its two residual branches per image with its rate and scales the
     kept ones by 1 / (1 - rate) (timm's `drop_path`, scale_by_keep=True), inside the proj / fc2 GEMM epilogues; in
     eval mode and at rate 0 nothing changes.  Plain attributes, no parameter or buffer: `state_dict()` and
-    checkpoints are unchanged.
+    checkpoints are unchanged;
+  * `model.patch_drop_rate` — patch dropout (timm's patch_drop_rate), from `ViTConfig(patch_drop_rate=...)` and
+    settable (a number in [0, 1)).  In training mode every image keeps `config.patch_keep_count(N, rate)` of its N
+    patch tokens — patch 0, the token the classifier reads, always, the others a uniform random subset drawn per image
+    and per step on the device (vit_patch_keep, no host sync) — plus the CLS token, in ascending order with CLS last;
+    the selection happens after `+ pos`, dropped patches are never embedded, and every block runs on T' = K + 1
+    tokens.  `model(x, keep_indices=idx)` takes the table from the caller instead (int32 / int64 [B, K], ascending,
+    column 0 equal to 0; checked for shape and dtype only), and `model.last_patch_keep` is the table the last
+    training forward used ([B, K] int32 on the model's device, None before one).  Eval mode and rate 0 are exactly the
+    model without the keyword.  A plain attribute: `state_dict()` and checkpoints are unchanged.
 
 Device semantics (the reference picks 'cuda' or 'cpu', train.py:26): a model on a ROCm device runs the fused HIP
 engine and fails loudly when libvit_hip.so is missing; a model on the CPU runs the host path `_cpu.py` (plain torch
@@ -126,8 +135,19 @@ class VisionTransformer(nn.Module):
         )
         self.store_attention_probs = None        # auto (module docstring); True / False force it
         self.drop_path_rates = _config.drop_path_rates(getattr(config, "drop_path_rate", 0.0), config.num_blocks)
+        self.patch_drop_rate = getattr(config, "patch_drop_rate", 0.0)
+        self.last_patch_keep = None
         self._engine = None
         self._anchor = None
+
+    @property
+    def patch_drop_rate(self):
+        """Patch-dropout rate of training forwards (module docstring); assign a number in [0, 1)."""
+        return self.__dict__.get("_patch_drop_rate", 0.0)       # (0: a model pickled before the attribute)
+
+    @patch_drop_rate.setter
+    def patch_drop_rate(self, rate):
+        self.__dict__["_patch_drop_rate"] = _config.check_patch_drop_rate(rate)
 
     @property
     def vit_config(self):
@@ -232,17 +252,20 @@ class VisionTransformer(nn.Module):
                 "engine is a single autograd node, so DDP's per-parameter reducer would never see the gradients. "
                 "Call model.enable_data_parallel() instead (bucketed RCCL all-reduce overlapped with the backward).")
 
-    def forward(self, x):
+    def forward(self, x, keep_indices=None):
         if not x.is_cuda and all(not p.is_cuda for p in (self.mlp[3].weight, self.emdeddings.pos_embd)):
-            return _cpu.vit_forward(self, x)              # host path: the model lives on the CPU (train.py:26)
+            # host path: the model lives on the CPU (train.py:26)
+            return _cpu.vit_forward(self, x, keep_indices=keep_indices)
         self._check_not_ddp_wrapped()
         eng = self.hip_engine
         want_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if want_grad:
             if self._anchor is None or self._anchor.device != x.device:
                 self._anchor = torch.zeros((), device=x.device, requires_grad=True)
-            return ViTFunction.apply(x, self._anchor, eng, self.training, self.wants_attention_probs(x.shape[0]))
-        logits, _ = eng.forward(x, self.training, save=False, want_probs=self.wants_attention_probs(x.shape[0]))
+            return ViTFunction.apply(x, self._anchor, eng, self.training, self.wants_attention_probs(x.shape[0]),
+                                     keep_indices)
+        logits, _ = eng.forward(x, self.training, save=False, want_probs=self.wants_attention_probs(x.shape[0]),
+                                keep=keep_indices)
         return logits
 
     def attention_rollout(self, x, token=0, head_fusion="mean", return_layers=False, fast_attention=False):

@@ -578,6 +578,10 @@ def main():
                          "the one above (timm's rule; turns --fuse-groups on; default: none)")
     ap.add_argument("--fuse-groups", action="store_true",
                     help="step every param group in one launch instead of one launch per group")
+    ap.add_argument("--patch-drop", type=float, default=0.0, metavar="RATE",
+                    help="patch dropout: each training image keeps max(1, int(N * (1 - RATE))) of its N patch tokens "
+                         "(patch 0 and a random subset) plus CLS, and the blocks run on those alone (timm's "
+                         "patch_drop_rate; default 0: off, as the reference); evaluation uses every token")
     ap.add_argument("--drop-path", type=float, default=0.0, metavar="RATE",
                     help="stochastic depth: drop each residual branch per image, block l of L at rate RATE * l / (L - 1) "
                          "(timm's linear rule; DeiT-B trains with 0.1; default 0: off, as the reference)")
@@ -663,7 +667,8 @@ def main():
     D, H, L = config.PRESETS[args.model]
     cfg = config.ViTConfig(input_channels=3, num_classes=args.classes, num_patches=n_patches, embedding_size=D,
                            patch_size=args.patch, num_heads=H, num_blocks=L, precision=dtype,
-                           batch_size=args.batch, device="cpu", drop_path_rate=args.drop_path)
+                           batch_size=args.batch, device="cpu", drop_path_rate=args.drop_path,
+                           patch_drop_rate=args.patch_drop)
     mix = None
     if args.mixup > 0 or args.cutmix > 0:
         from VisionTransformer.data import BatchMix
