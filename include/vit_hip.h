@@ -86,7 +86,8 @@ const char* vit_last_error(void);
  * vit_attn_rollout_workspace_bytes, vit_attn_rollout_step and vit_attn_rollout_step_form (attention rollout), with no
  * option name: the form is an argument of the third;
  * vit_patch_keep, vit_im2col_gather, vit_gather_pos, vit_pos_grad_gather and vit_col2im_scatter (patch dropout), with
- * no option name.
+ * no option name;
+ * vit_softmax_xent_distill (knowledge distillation against a frozen teacher's logits), with no option name.
  * vit_set_option returns VIT_ERR_INVALID for an unknown name; vit_get_option returns INT64_MIN for one. */
 int vit_set_option(const char* name, int64_t value);
 int64_t vit_get_option(const char* name);
@@ -336,6 +337,33 @@ int vit_softmax_xent(const float* logits, const int64_t* labels, int64_t rows, i
 int vit_softmax_xent_mixed(const float* logits, const int64_t* labels_a, const int64_t* labels_b /* may be NULL */,
                            const float* lam /* device, [rows]; may be NULL */, float smoothing, int64_t rows,
                            int64_t classes, float* loss, float* dlogits, float* workspace, void* stream);
+/* Knowledge distillation: vit_softmax_xent_mixed blended with a term against a frozen teacher's logits, in one launch
+ * over the rows (vit_distill.hip).  For student row x, teacher row z, C = classes:
+ *   t      the target of vit_softmax_xent_mixed (same labels_a / labels_b / lam / smoothing rules);
+ *   p = softmax(x),  p_tau = softmax(x / tau),  q_tau = softmax(z / tau);
+ *   base_r = lse(x) - sum_c t * x             exactly vit_softmax_xent_mixed's row term;
+ *   VIT_DISTILL_SOFT:  d_r = tau^2 * KL(q_tau || p_tau),   g_r = tau * (p_tau - q_tau);
+ *   VIT_DISTILL_HARD:  yhat = the LOWEST index at which z attains its maximum,
+ *                      d_r = lse(x) - x[yhat],             g_r = p - onehot(yhat);   tau is ignored (but checked);
+ *   loss    = mean_r((1 - alpha) * base_r + alpha * d_r),
+ *   dlogits = ((1 - alpha) * (p - t) + alpha * g_r) / rows.
+ * The soft form is Hinton's loss with "batchmean" reduction: F.kl_div(log_softmax(x / tau), log_softmax(z / tau),
+ * reduction="batchmean", log_target=True) * tau^2.  DeiT's script divides the KL by rows * C instead; a caller who
+ * wants that weighting scales alpha.  No gradient is formed for the teacher.
+ * alpha = 0 with a finite teacher gives the loss and dlogits of vit_softmax_xent_mixed bit for bit.  A label outside
+ * [0, classes) gives a NaN loss and no stray read.  A NaN in a row of either input makes that row's gradient and the
+ * loss NaN and leaves every other row's gradient as it is; inputs are otherwise assumed finite.  No atomics: bitwise
+ * repeatable.  workspace: rows floats.  `lam` is DEVICE memory, [rows].
+ * Refused (VIT_ERR_INVALID) before any launch: a NULL logits / teacher_logits / labels_a / loss / dlogits /
+ * workspace; rows or classes <= 0, rows > 2^31 - 1; smoothing outside [0, 1) or NaN; lam without labels_b; a kind
+ * other than the two; alpha outside [0, 1] or NaN; tau not finite or <= 0. */
+typedef enum { VIT_DISTILL_SOFT = 0, VIT_DISTILL_HARD = 1 } vit_distill_kind;
+int vit_softmax_xent_distill(const float* logits, const float* teacher_logits, const int64_t* labels_a,
+                             const int64_t* labels_b /* may be NULL */,
+                             const float* lam /* device, [rows]; may be NULL */, float smoothing,
+                             int32_t kind /* VIT_DISTILL_SOFT = 0, VIT_DISTILL_HARD = 1 */, float alpha, float tau,
+                             int64_t rows, int64_t classes, float* loss, float* dlogits,
+                             float* workspace /* rows floats */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Image pipeline of the training loader (train.py:151-155: convert('RGB') -> transforms.Resize((S, S)) ->

@@ -164,6 +164,7 @@ _SIGS = {
     "vit_gather_pos": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "vit_pos_grad_gather": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _I64, _I64, _I64, _F, _P]),
     "vit_col2im_scatter": (ctypes.c_int, [_P, _I32, _P, _P, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+    "vit_softmax_xent_distill": (ctypes.c_int, [_P, _P, _P, _P, _P, _F, _I32, _F, _F, _I64, _I64, _P, _P, _P, _P]),
 }
 
 EPI_BDR, EPI_SLAB, EPI_GENERAL, EPI_BDRS = 3, 4, 5, 8    # VIT_EPI_* (vit_hip.h): kinds vit_gemm_kernel_choice reports
@@ -172,6 +173,7 @@ DROP_PATH_MAX_LAYERS = 64    # VIT_DROP_PATH_MAX_LAYERS (vit_hip.h)
 EVAL_MAXK = 16               # VIT_EVAL_MAXK (vit_hip.h)
 PATCH_KEEP_MAX_N = 4096      # VIT_PATCH_KEEP_MAX_N (vit_hip.h)
 ROLLOUT_MEAN, ROLLOUT_MAX, ROLLOUT_MIN = 0, 1, 2             # VIT_ROLLOUT_* (vit_hip.h)
+DISTILL_SOFT, DISTILL_HARD = 0, 1                            # VIT_DISTILL_* (vit_hip.h)
 ROLLOUT_FORM_AUTO, ROLLOUT_FORM_VALU, ROLLOUT_FORM_MFMA = 0, 1, 2   # `form` of vit_attn_rollout_step_form
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

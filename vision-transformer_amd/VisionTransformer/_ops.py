@@ -498,6 +498,53 @@ def softmax_xent_mixed(logits, labels_a, labels_b=None, lam=None, smoothing=0.0,
     return loss, dlogits
 
 
+DISTILL_KINDS = {"soft": _lib.DISTILL_SOFT, "hard": _lib.DISTILL_HARD}
+
+
+def check_distill_args(kind, alpha, tau):
+    """ValueError unless `kind` is "soft" / "hard", 0 <= alpha <= 1 and tau is finite and positive (the conditions of
+    vit_softmax_xent_distill, checked before any launch)."""
+    if kind not in DISTILL_KINDS:
+        raise ValueError(f"distillation kind must be 'soft' or 'hard' (got {kind!r})")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"distillation alpha must lie in [0, 1] (got {alpha!r})")
+    if not (0.0 < tau < float("inf")):
+        raise ValueError(f"distillation tau must be finite and positive (got {tau!r})")
+
+
+def softmax_xent_distill(logits, teacher_logits, labels_a, labels_b=None, lam=None, smoothing=0.0, kind="soft",
+                         alpha=0.5, tau=1.0, stream=None):
+    """vit_softmax_xent_distill: (1 - alpha) * softmax_xent_mixed's loss + alpha * the distillation term against
+    `teacher_logits` (float32, the logits' shape and device): kind "soft" tau^2 * KL(softmax(z / tau) || softmax(x /
+    tau)) with batchmean reduction, kind "hard" the cross entropy against the teacher's lowest arg max.  Labels as
+    softmax_xent_mixed takes them.  Returns (loss [1] f32, dlogits [rows, classes] f32); no gradient for the teacher."""
+    _need_cuda(logits, teacher_logits, labels_a, labels_b, lam)
+    check_distill_args(kind, alpha, tau)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous float32 [rows, classes] tensor")
+    rows, classes = logits.shape
+    if (teacher_logits.shape != logits.shape or teacher_logits.dtype != torch.float32
+            or not teacher_logits.is_contiguous() or teacher_logits.device != logits.device):
+        raise ValueError(f"teacher_logits must be a contiguous float32 tensor of shape {tuple(logits.shape)} on the "
+                         f"logits' device (got {tuple(teacher_logits.shape)}, {teacher_logits.dtype})")
+    for name, t, dt in (("labels_a", labels_a, torch.int64), ("labels_b", labels_b, torch.int64),
+                        ("lam", lam, torch.float32)):
+        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()
+                              or t.device != logits.device):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {rows} elements on the logits' device")
+    if lam is not None and labels_b is None:
+        raise ValueError("lam given without labels_b")
+    if not 0.0 <= smoothing < 1.0:
+        raise ValueError(f"label smoothing must lie in [0, 1) (got {smoothing!r})")
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    ws = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    _lib.call("vit_softmax_xent_distill", _ptr(logits), _ptr(teacher_logits), _ptr(labels_a), _ptr(labels_b),
+              _ptr(lam), float(smoothing), DISTILL_KINDS[kind], float(alpha), float(tau), rows, classes, _ptr(loss),
+              _ptr(dlogits), _ptr(ws), _stream(stream))
+    return loss, dlogits
+
+
 def eval_update(logits, labels, counts, loss_sum, confusion=None, rows=None, maxk=None, stream=None):
     """vit_eval_update: score the first `rows` rows of `logits` (float32 [R, classes], unit column stride, any row
     stride) against `labels` (int64, at least `rows` of them) and ACCUMULATE into `counts` (int64 [2 + maxk]),

@@ -725,6 +725,64 @@ def cross_entropy(logits, labels, label_smoothing=0.0):
                               labels.lam.contiguous().float(), float(label_smoothing))
 
 
+class _DistillFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, teacher_logits, a, b, lam, smoothing, kind, alpha, tau):
+        loss, dlogits = _ops.softmax_xent_distill(logits.contiguous().float(), teacher_logits, a, b, lam, smoothing,
+                                                  kind, alpha, tau)
+        ctx.save_for_backward(dlogits)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits * g,) + (None,) * 8
+
+
+def lowest_argmax(z):
+    """[rows] int64: the lowest index at which each row of `z` attains its maximum (torch.argmax leaves the choice
+    among ties open)."""
+    C = z.shape[-1]
+    idx = torch.arange(C, device=z.device).expand_as(z)
+    return torch.where(z == z.max(dim=-1, keepdim=True).values, idx, C).min(dim=-1).values
+
+
+def distillation_loss(logits, labels, teacher_logits, *, kind="soft", alpha=0.5, tau=1.0, label_smoothing=0.0):
+    """(1 - alpha) * cross_entropy(logits, labels, label_smoothing) + alpha * d, the loss of a student trained against
+    the logits of a frozen teacher (Hinton et al. 2015; DeiT, Touvron et al. 2021) — one fused HIP kernel
+    (vit_softmax_xent_distill), gradient precomputed; not in the reference.
+
+    kind "soft": d = tau^2 * KL(softmax(teacher / tau) || softmax(logits / tau)), summed over the classes and averaged
+    over the rows: F.kl_div(log_softmax(logits / tau), log_softmax(teacher / tau), reduction="batchmean",
+    log_target=True) * tau^2.  DeiT's script divides the sum by rows * classes instead; scale `alpha` for its weighting.
+    kind "hard": d = cross_entropy(logits, yhat), yhat the lowest index of each teacher row's maximum; `tau` is unused.
+    `labels`: a label tensor or MixedLabels, as cross_entropy takes them.  `teacher_logits` is detached whatever the
+    caller passes: no gradient reaches the teacher.  Host tensors run the same formula in torch ops."""
+    _ops.check_distill_args(kind, alpha, tau)
+    _check_label_smoothing(label_smoothing)
+    if teacher_logits.shape != logits.shape:
+        raise ValueError(f"teacher_logits must have the logits' shape {tuple(logits.shape)} "
+                         f"(got {tuple(teacher_logits.shape)})")
+    z = teacher_logits.detach()
+    mixed = isinstance(labels, MixedLabels)
+    if not logits.is_cuda:
+        F = nn.functional
+        z = z.to(logits.dtype)
+        base = F.cross_entropy(logits, dense_target(labels, logits.shape[-1], label_smoothing, dtype=logits.dtype))
+        if kind == "soft":
+            d = F.kl_div(F.log_softmax(logits / tau, dim=-1), F.log_softmax(z / tau, dim=-1), reduction="batchmean",
+                         log_target=True) * tau ** 2
+        else:
+            d = F.cross_entropy(logits, lowest_argmax(z))
+        return (1.0 - alpha) * base + alpha * d
+    z = z.contiguous().float()
+    if mixed:
+        a, b, lam = labels.a.contiguous().long(), labels.b.contiguous().long(), labels.lam.contiguous().float()
+    else:
+        a, b, lam = labels.contiguous().long(), None, None
+    return _DistillFn.apply(logits, z, a, b, lam, float(label_smoothing), kind, float(alpha), float(tau))
+
+
 def _check_max_grad_norm(max_grad_norm):
     if max_grad_norm is not None and not (0 < max_grad_norm < math.inf):
         raise ValueError(f"max_grad_norm must be None or a positive finite number (got {max_grad_norm!r})")

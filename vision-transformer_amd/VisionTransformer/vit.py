@@ -306,3 +306,47 @@ class VisionTransformer(nn.Module):
             raise ValueError(f"patch_map: maps must be [B, {N + 1}] and image_hw give {N} patches of {P} x {P}, got "
                              f"{tuple(maps.shape)} and {gh} x {gw}")
         return maps[:, :N].reshape(maps.shape[0], gh, gw)
+
+
+def load_teacher(config, checkpoint, *, student=None, ema=False, device=None):
+    """The frozen teacher of a distillation run (optim.distillation_loss): a VisionTransformer(config) with the
+    "model_state_dict" (`ema`: the "ema_state_dict") of `checkpoint` — a checkpoint file, or a directory, of which the
+    newest N.pt is read as train.search_checkpoint finds it — moved to `device`, in eval mode, every parameter with
+    requires_grad False, and `store_attention_probs` False: its forward under no_grad keeps no tape and no
+    probabilities.  `student` (a ViTConfig or a model): the teacher must share its num_classes, and its batch_size
+    because the CLS parameter is batch-shaped (vit.py:32); preset, depth, width, patch size and compute dtype are the
+    teacher's own, as long as it takes the student's input."""
+    import glob
+    import re
+    if student is not None:
+        s = getattr(student, "vit_config", student)
+        for field in ("num_classes", "batch_size"):
+            if getattr(config, field) != getattr(s, field):
+                raise ValueError(f"load_teacher: the teacher's {field} ({getattr(config, field)}) differs from the "
+                                 f"student's ({getattr(s, field)}): the two models must score the same classes on the "
+                                 "same batch (the CLS parameter is batch-shaped)")
+    path = os.fspath(checkpoint)
+    if os.path.isdir(path):
+        nums = [int(m.group(1)) for m in (re.match(r"(\d+)(?=\.pt)", os.path.basename(f))
+                                          for f in glob.glob(os.path.join(path, "*.pt"))) if m]
+        if not nums:
+            raise FileNotFoundError(f"load_teacher: no checkpoint (N.pt) in {path!r}")
+        path = os.path.join(path, f"{max(nums)}.pt")
+    elif not os.path.isfile(path):
+        raise FileNotFoundError(f"load_teacher: no checkpoint at {path!r}")
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    key = "ema_state_dict" if ema else "model_state_dict"
+    if key not in ckpt:
+        raise KeyError(f"load_teacher: {path!r} has no {key!r}"
+                       + (" (it was trained without a weight EMA)" if ema else ""))
+    model = VisionTransformer(config)
+    try:
+        model.load_state_dict(ckpt[key])
+    except RuntimeError as e:
+        raise ValueError(f"load_teacher: {path!r} does not hold a model of {config!r}: {e}") from None
+    if device is not None:
+        model = model.to(device)
+    model.eval()
+    model.requires_grad_(False)
+    model.store_attention_probs = False
+    return model

@@ -31,8 +31,8 @@ import torch
 import torch.distributed as dist
 
 from VisionTransformer import config, vit
-from VisionTransformer.optim import (LRSchedule, MixedLabels, cross_entropy, make_optimizer, param_groups_layer_decay,
-                                     param_groups_weight_decay)
+from VisionTransformer.optim import (LRSchedule, MixedLabels, cross_entropy, distillation_loss, make_optimizer,
+                                     param_groups_layer_decay, param_groups_weight_decay)
 
 device = "cuda" if torch.cuda.is_available() else "cpu"
 
@@ -292,11 +292,28 @@ def _schedule(optimizer, sched, layer_decay, total_steps, warmup_steps, warmup_l
     return LRSchedule(optimizer, sched or "constant", total_steps, warmup_steps, warmup_lr, min_lr)
 
 
+def _check_teacher(teacher, configs, distill, distill_alpha, distill_tau):
+    """The conditions of a distillation run, before anything is built: the loss's arguments, and a frozen eval-mode
+    teacher that scores the student's classes on the student's batch."""
+    if teacher is None:
+        return
+    from VisionTransformer._ops import check_distill_args
+    check_distill_args(distill, distill_alpha, distill_tau)
+    tc = teacher.vit_config
+    for field in ("num_classes", "batch_size"):
+        if getattr(tc, field) != getattr(configs, field):
+            raise ValueError(f"the teacher's {field} ({getattr(tc, field)}) differs from the student's "
+                             f"({getattr(configs, field)})")
+    if teacher.training or any(p.requires_grad for p in teacher.parameters()):
+        raise ValueError("the teacher must be frozen and in eval mode (vit.load_teacher)")
+
+
 def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkpoint_dir, lr=1e-4,
           log_every=1, max_steps=None, reference_loop=False, max_grad_norm=None, ema_decay=None,
           label_smoothing=0.0, mix=None, opt="adamw", weight_decay=1e-4, no_decay_1d=False, always_adapt=False,
           trust_clip=False, sched=None, warmup_steps=0, warmup_lr=0.0, min_lr=0.0, layer_decay=None,
-          fuse_groups=False, val_topk=None, val_confusion=False):
+          fuse_groups=False, val_topk=None, val_confusion=False, teacher=None, distill="soft", distill_alpha=0.5,
+          distill_tau=1.0):
     """The reference training loop (train.py:60-119) on the HIP path.  Returns the last epoch's summed loss.
 
     Defaults keep the GPU busy: no host sync inside the epoch — the epoch loss is summed on the device and the per-step
@@ -344,7 +361,17 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
     epoch's validation is validate() instead of evaluate() — on the EMA weights when there are any — with no host read
     until its end.  "val?acc" is then its top-1, rounded as before, "Loss/val" and "Acc{k}/val" are logged and printed
     beside it, and the checkpoint dict gains one key, "val_metrics": validate()'s dict, the confusion matrix as nested
-    lists.  k = 1 is always among the k.  None (the default) is the loop, the tags and the checkpoint dict above."""
+    lists.  k = 1 is always among the k.  None (the default) is the loop, the tags and the checkpoint dict above.
+
+    `teacher`, `distill`, `distill_alpha`, `distill_tau` (not in the reference): knowledge distillation.  `teacher` is
+    a frozen model (vit.load_teacher) on the run's device with the student's class count and batch size; every step
+    runs it under no_grad on the batch the student sees — after mixup / CutMix, as DeiT does; in eval mode, so on every
+    patch even under patch dropout — and the loss is optim.distillation_loss(logits, labels, teacher logits,
+    kind=distill, alpha=distill_alpha, tau=distill_tau, label_smoothing=label_smoothing).  The logged
+    "Loss/train_batch", the epoch loss and the checkpoint's "loss" are that combined loss.  The teacher is in no
+    optimizer, EMA, gradient bucket or checkpoint, and validation scores the student.  None (the default) is the loop,
+    its launches, its tags and the checkpoint dict above."""
+    _check_teacher(teacher, configs, distill, distill_alpha, distill_tau)
     rank, world = _rank_world()
     saved_epoch = search_checkpoint(checkpoint_dir)
     torch.manual_seed(0)                              # identical init on every rank
@@ -400,8 +427,14 @@ def train(configs, train_loader, test_loader, epochs, eval_iter, log_dir, checkp
                 labels = labels.to(device, non_blocking=True)
                 if mix is not None:
                     tensors, labels = mix(tensors, labels)
-            logits = net(tensors)
-            loss = cross_entropy(logits, labels, label_smoothing)
+            if teacher is None:
+                logits = net(tensors)
+                loss = cross_entropy(logits, labels, label_smoothing)
+            else:
+                with torch.no_grad():
+                    teacher_logits = teacher(tensors)
+                loss = distillation_loss(net(tensors), labels, teacher_logits, kind=distill, alpha=distill_alpha,
+                                         tau=distill_tau, label_smoothing=label_smoothing)
             optimizer.zero_grad(set_to_none=True)
             loss.backward()
             optimizer.step()
@@ -502,14 +535,18 @@ def eval_only(configs, test_loader, checkpoint_dir, topk=(1, 5), confusion=True,
 
 def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_norm=None, ema_decay=None,
                label_smoothing=0.0, mix=None, opt="adamw", weight_decay=1e-4, no_decay_1d=False, always_adapt=False,
-               trust_clip=False, layer_decay=None, fuse_groups=False):
+               trust_clip=False, layer_decay=None, fuse_groups=False, teacher=None, distill="soft", distill_alpha=0.5,
+               distill_tau=1.0):
     """The hot loop body (train.py:91-98: forward, CE loss, zero_grad(set_to_none), backward, AdamW step) on one
     synthetic batch already resident on `dev`, dropout on; returns (seconds per timed step, last loss).  This is the
     repo's own CPU training step that bench.py's `cpu_baseline` times (BASELINE config 1).  Unclipped unless
     `max_grad_norm` is given, and without a weight EMA unless `ema_decay` is.  With `mix` (a data.BatchMix) every step
     first mixes the resident batch, and `label_smoothing` goes to the loss, as in train().  `opt`, `weight_decay`,
     `no_decay_1d`, `always_adapt`, `trust_clip`, `layer_decay` and `fuse_groups` choose the optimizer as in train()
-    (with `layer_decay` under a constant schedule, applied once: the rates do not move while timing)."""
+    (with `layer_decay` under a constant schedule, applied once: the rates do not move while timing).  `teacher`,
+    `distill`, `distill_alpha` and `distill_tau` are train()'s: the step then runs the teacher's forward under no_grad
+    and optim.distillation_loss."""
+    _check_teacher(teacher, configs, distill, distill_alpha, distill_tau)
     dev = torch.device(dev or device)
     torch.manual_seed(0)
     model = vit.VisionTransformer(configs).to(dev).train()
@@ -529,7 +566,13 @@ def time_steps(configs, steps, warmup, lr=1e-4, dev=None, seed=1234, max_grad_no
                 torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
         xb, yb = (x, y) if mix is None else mix(x, y)
-        loss = cross_entropy(model(xb), yb, label_smoothing)
+        if teacher is None:
+            loss = cross_entropy(model(xb), yb, label_smoothing)
+        else:
+            with torch.no_grad():
+                teacher_logits = teacher(xb)
+            loss = distillation_loss(model(xb), yb, teacher_logits, kind=distill, alpha=distill_alpha, tau=distill_tau,
+                                     label_smoothing=label_smoothing)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
@@ -631,6 +674,22 @@ def main():
     ap.add_argument("--rollout-token", type=int, default=0, metavar="I",
                     help="with --rollout-out: the token whose rollout is taken (0: the one the classifier reads; the "
                          "CLS token is the last)")
+    ap.add_argument("--teacher-checkpoint", default=None, metavar="PATH",
+                    help="knowledge distillation: train against the logits of the frozen model in this checkpoint file "
+                         "or directory (its newest N.pt), run under no_grad on every training batch (default: none)")
+    ap.add_argument("--teacher-model", default=None, choices=sorted(config.PRESETS),
+                    help="with --teacher-checkpoint: the teacher's preset (default: --model)")
+    ap.add_argument("--teacher-dtype", default=None, choices=["fp32", "bf16"],
+                    help="with --teacher-checkpoint: the teacher's compute dtype (default: --dtype)")
+    ap.add_argument("--teacher-ema", action="store_true",
+                    help="with --teacher-checkpoint: load the checkpoint's ema_state_dict")
+    ap.add_argument("--distill", default=None, choices=["soft", "hard"],
+                    help="with --teacher-checkpoint: soft (default) = tau^2 * KL(teacher || student) at temperature "
+                         "--distill-tau, hard = cross entropy against the teacher's arg max")
+    ap.add_argument("--distill-alpha", type=float, default=None, metavar="F",
+                    help="with --teacher-checkpoint: loss = (1 - F) * cross entropy + F * distillation term (default 0.5)")
+    ap.add_argument("--distill-tau", type=float, default=None, metavar="F",
+                    help="with --teacher-checkpoint: temperature of the soft term (default 1)")
     ap.add_argument("--reference-loop", action="store_true",
                     help="the reference's loop bookkeeping exactly: validate every epoch, restart the step counter on "
                          "resume, host-summed loss (train.py:60-119)")
@@ -712,10 +771,36 @@ def main():
         ap.error("--rollout-images must be positive")
     if not 0 <= args.rollout_token <= n_patches:
         ap.error(f"--rollout-token must lie in [0, {n_patches}]")
+    teacher_flags = (args.teacher_model, args.teacher_dtype, args.distill, args.distill_alpha, args.distill_tau)
+    if args.teacher_checkpoint is None and (args.teacher_ema or any(v is not None for v in teacher_flags)):
+        ap.error("--teacher-model, --teacher-dtype, --teacher-ema, --distill, --distill-alpha and --distill-tau need "
+                 "--teacher-checkpoint")
+    distill_kw = {}
+    if args.teacher_checkpoint is not None and not args.eval_only:
+        from VisionTransformer._ops import check_distill_args
+        distill_kw = dict(distill=args.distill or "soft",
+                          distill_alpha=0.5 if args.distill_alpha is None else args.distill_alpha,
+                          distill_tau=1.0 if args.distill_tau is None else args.distill_tau)
+        try:
+            check_distill_args(*distill_kw.values())
+        except ValueError as e:
+            ap.error(str(e))
+        tD, tH, tL = config.PRESETS[args.teacher_model or args.model]
+        tdtype = dtype if args.teacher_dtype is None else \
+            (torch.bfloat16 if args.teacher_dtype == "bf16" else torch.float32)
+        tcfg = config.ViTConfig(input_channels=3, num_classes=args.classes, num_patches=n_patches, embedding_size=tD,
+                                patch_size=args.patch, num_heads=tH, num_blocks=tL, precision=tdtype,
+                                batch_size=args.batch, device="cpu")
+        try:
+            distill_kw["teacher"] = vit.load_teacher(tcfg, args.teacher_checkpoint, student=cfg, ema=args.teacher_ema,
+                                                     device=device)
+        except (FileNotFoundError, KeyError, ValueError) as e:
+            ap.exit(2, f"train.py --teacher-checkpoint: {e}\n")
     if args.bench:
         steps = args.steps or 30
         sec, last = time_steps(cfg, steps, args.warmup, lr=args.lr, max_grad_norm=args.clip_grad_norm,
-                               ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix, **opt_args)
+                               ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix, **opt_args,
+                               **distill_kw)
         print(json.dumps({"device": device, "model": args.model, "img": args.img, "batch": args.batch,
                           "dtype": args.dtype, "threads": torch.get_num_threads(), "warmup": args.warmup,
                           "steps": steps, "ms_per_step": round(sec * 1e3, 3),
@@ -781,7 +866,8 @@ def main():
           lr=args.lr, max_steps=args.steps, reference_loop=args.reference_loop, max_grad_norm=args.clip_grad_norm,
           ema_decay=args.ema_decay, label_smoothing=args.label_smoothing, mix=mix, sched=args.sched,
           warmup_steps=args.warmup_steps, warmup_lr=args.warmup_lr, min_lr=args.min_lr,
-          val_topk=tuple(args.val_topk) if args.val_topk else None, val_confusion=args.val_confusion, **opt_args)
+          val_topk=tuple(args.val_topk) if args.val_topk else None, val_confusion=args.val_confusion, **opt_args,
+          **distill_kw)
     if world > 1:
         dist.destroy_process_group()
 
